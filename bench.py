@@ -7,6 +7,15 @@ closed-loop states of LMPC_N20_sys_full.mat cycled to 1024, fp64, inputs residen
 through bqp_solve_ocp_batched_device (one solve-kernel launch).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config C2|C3|C4|C5] [--batch B]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (value, ms_per_step,
+the exit-flag summary of the last timed step).  --full adds everything that takes runs of its
+own: the two-group pass, the isolated-launch pass, the KKT-residual step and the comparisons
+with the stored optima (check), the roofline (K_ref from the C restatement) and the CPU baseline.
+--dump-outputs DIR writes the arrays the last timed step returned to its caller (rank 0's shard)
+as DIR/<name>.npy; the inputs of a config are the same in every run, so two builds can be
+compared output for output.
 
 Other configs - measured the same way, reported in DESIGN.md:
   C3  trackingMPC double integrator (F5), N=30, 22-row terminal set, 4096 per GPU (1024 x0 x 4
@@ -21,7 +30,7 @@ own shard (no collective in the timed region); the first moves and exit flags ar
 once after timing (RCCL over xGMI) - bqp.dist.  `--dry-run` rehearses the same multi-rank code
 on CPU (gloo, stub solver; tests/test_bench_dist.py).
 
-Prints ONE JSON line (rank 0): value = QP-steps/s over all ranks; roofline of the solve kernel
+Prints ONE JSON line (rank 0): value = QP-steps/s over all ranks; with --full, roofline of the solve kernel
 (algorithmic FP64 flops / kernel time from hipEvents on the launch stream; HBM traffic from the
 committed rocprofv3 PMC summary profiles/pmc_latest.json); the CPU baseline (oracle/cpu_ipm.c,
 the same algorithm in C, OpenMP over host cores, bounded sample).
@@ -245,6 +254,29 @@ def cll_cpu_baseline(g, X0, threads):
                         '%(n)s); oracle/cpu_lbmpc.c (same algorithm, fp64, -O3 -march=native, OpenMP)')
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: DIR/<name>.npy for every array of `arrays` (leading axis = instance), as
+    float64 (float32 stays float32).  At most 64 MB in all: a larger set is cut to the same
+    fixed, seeded sample of instances in every run (rows.npy holds their indices)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        arrs[k] = np.ascontiguousarray(v, dtype=np.float32 if v.dtype == np.float32 else np.float64)
+    rows = len(next(iter(arrs.values())))
+    per_row = sum(a.nbytes for a in arrs.values()) / max(rows, 1) + 8
+    keep = int((DUMP_CAP_BYTES - 4096 * (len(arrs) + 1)) // per_row)
+    if keep < rows:
+        sel = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrs = {k: a[sel] for k, a in arrs.items()}
+        arrs['rows'] = sel.astype(np.float64)
+    for k, a in arrs.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a)
+
+
 def free_port():
     import socket
     s = socket.socket()
@@ -350,6 +382,13 @@ class GpuSolver:
         st = self.sets[0]
         return st['ou'][:, 0, :].contiguous(), st['oe']
 
+    def results(self):
+        """what the last step() returned to its caller: state and input trajectories, theta,
+        objective value and exit flag of every instance (host copies)"""
+        st = self.sets[self.last]
+        return {k: st[o].cpu().numpy() for k, o in
+                (('x', 'ox'), ('u', 'ou'), ('theta', 'ot'), ('fval', 'of'), ('exitflag', 'oe'))}
+
     def outputs(self):
         """per-instance exit statistics (bqp_output) of a step(with_out=True)"""
         raw = self.sets[0]['oo'].cpu().numpy().tobytes()
@@ -391,6 +430,9 @@ class StubSolver:
     def first_moves(self):
         return self.torch.from_numpy(self.u), self.torch.from_numpy(self.e)
 
+    def results(self):
+        return dict(u=self.u, exitflag=self.e)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -399,7 +441,16 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--config', default='C2', choices=['C1', 'C2', 'C2H', 'C2D', 'C3', 'C4', 'C5', 'CL', 'CLL'])
     ap.add_argument('--batch', type=int, default=0, help='per-GPU batch (C4: total)')
-    ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run what the headline figure does not need: the two-group and '
+                         'isolated-launch passes, the KKT-residual step and the comparisons with '
+                         'the stored optima, the roofline and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the arrays the last timed step returned '
+                         '(rank 0\'s shard; CL / CLL: the gathered trajectories) as DIR/<name>.npy, '
+                         'float64, at most 64 MB in all')
+    ap.add_argument('--no-cpu', action='store_true',
+                    help='with --full: skip the timed CPU baseline')
     ap.add_argument('--precision', default='fp64', choices=['fp64', 'fp32', 'mixed'],
                     help='structured solver arithmetic (C5 compares both)')
     ap.add_argument('--no-polish', action='store_true',
@@ -480,10 +531,12 @@ def main():
     t1 = time.perf_counter()
     elapsed = bd.max_over_ranks(t1 - t0, dev, world)
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in evs])) if evs else None
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, solver.results())
     # two independent plant groups (reported beside the value, never as it):
-    # the same steps with consecutive steps on two streams
+    # the same steps with consecutive steps on two streams (--full)
     two_groups = None
-    if not args.dry_run and solver.active == 1 and not args.no_two_groups:
+    if args.full and not args.dry_run and solver.active == 1 and not args.no_two_groups:
         solver.active = 2
         for _ in range(2):
             solver.step()
@@ -501,7 +554,7 @@ def main():
         solver.active = 1
     # one launch alone (separate pass, host-synchronised per step): the isolated launch time
     kernel_ms_alone = None
-    if not args.dry_run:
+    if args.full and not args.dry_run:
         kms = []
         for _ in range(min(args.steps, 20)):
             solver.step()
@@ -528,7 +581,7 @@ def main():
         uf, ef = StubSolver.moves(full)
         check['gather_matches_unsharded'] = bool(np.array_equal(u0_all, uf) and
                                                  np.array_equal(fl_all, ef))
-    if not args.dry_run:
+    if args.full and not args.dry_run:
         # KKT residuals of this batch at exit (bqp_output: stationarity, primal eq, primal
         # ineq, complementarity mu) and the first move against MATLAB's stored moves and the
         # exact optima of the fixtures
@@ -579,7 +632,7 @@ def main():
             check['value_two_groups'] = round(v2, 1)
             check['ms_per_step_two_groups'] = round(1e3 * two_groups / args.steps, 4)
         roof, cpu = None, None
-        if not args.dry_run:
+        if args.full and not args.dry_run:
             present = len(os.sched_getaffinity(0))
             threads = int(os.environ.get('OMP_NUM_THREADS', '0')) or present
             # the CPU baseline is timed at N=1 only (the multi-GPU lines carry K_ref, not a timing)
@@ -946,9 +999,13 @@ def bench_loop(args):
         check['gather_matches_unsharded'] = bool(all(np.array_equal(gathered[k], ref[k]) for k in names))
         check['x0_independent_of_world'] = bool(np.array_equal(full['X0'], X0_all))
     line = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: gathered[k] for k in names})
     if rank == 0:
         cpu, roof = None, None
-        if args.config == 'CLL' and not args.dry_run:
+        if not args.full:
+            pass                    # the stored-run comparison, roofline and CPU legs: --full
+        elif args.config == 'CLL' and not args.dry_run:
             g = wl['g']
             X0 = wl['X0']
             st = np.load(os.path.join(GOLD, 'dms_lbmpc_loops.npz'))['DMS_tLBMPC_q100']
@@ -997,7 +1054,7 @@ def bench_aux(args):
         one batched SQP solve (default batch 1 = the reference's single-instance config);
     C2H / C2D  the C2 workload through the host-pointer entry point / in quadprog form.
     The CPU leg of C1 is the numpy restatement (oracle/lbmpc.py, interpreted), on a bounded
-    sample.  The closed-loop configs CL / CLL run on N ranks: bench_loop."""
+    sample; it, C2D's roofline and its comparison with the exact optima run with --full.  The closed-loop configs CL / CLL run on N ranks: bench_loop."""
     import time as _t
     import torch
     import bqp
@@ -1016,6 +1073,7 @@ def bench_aux(args):
             r = bqp.solve_ocp(wl['prob'], wl['X'], handle=h)
         el = _t.perf_counter() - t0
         B = wl['X'].shape[0]
+        outs = {k: r[k] for k in ('x', 'u', 'theta', 'fval', 'exitflag')}
         line = dict(metric='QP-steps/s, host-pointer API (PCIe-inclusive)', value=round(B * args.steps / el, 1),
                     unit='QP-steps/s', n_gpus=1, steps=args.steps, warmup=args.warmup,
                     ms_per_step=round(1e3 * el / args.steps, 4), higher_is_better=True, scaling='weak',
@@ -1068,24 +1126,30 @@ def bench_aux(args):
         torch.cuda.synchronize()
         el = _t.perf_counter() - t0
         Z = ox.cpu().numpy()
-        u, th, x = cd.recover(Z, wl['X'])
-        g2 = np.load(os.path.join(GOLD, 'lmpc_N20.npz'))
-        du_star = g2['du_star']
-        sel = np.flatnonzero(np.isin(wl['gidx'], g2['idx']))
-        pos = {int(v): i for i, v in enumerate(g2['idx'])}
-        err = max(abs(u[i, 0, 0] - du_star[pos[int(wl['gidx'][i])]]) for i in sel) if len(sel) else None
+        outs = dict(x=Z, fval=ofv.cpu().numpy(), exitflag=oe.cpu().numpy(), lam=lam.cpu().numpy())
+        err = None
+        if args.full:
+            # the first move against the exact optima of the fixture
+            u, th, x = cd.recover(Z, wl['X'])
+            g2 = np.load(os.path.join(GOLD, 'lmpc_N20.npz'))
+            du_star = g2['du_star']
+            sel = np.flatnonzero(np.isin(wl['gidx'], g2['idx']))
+            pos = {int(v): i for i, v in enumerate(g2['idx'])}
+            err = max(abs(u[i, 0, 0] - du_star[pos[int(wl['gidx'][i])]]) for i in sel) if len(sel) else None
         kms_mean = float(np.mean(kms))
         flops_iter = m * n * n + n ** 3 / 3.0 + 8.0 * m * n          # A'DA (MFMA), Cholesky, mat-vecs
         its = None
         try:
+            # the iteration counts (roofline) take a host-pointer solve of their own: --full
             out = (_lib.Output * B)()
-            rc = lib.bqp_quadprog_batched(h.value, C.byref(dims), B, C.byref(strides),
-                                          _lib.ptr(np.ascontiguousarray(cd.H.T)), _lib.ptr(f),
-                                          _lib.ptr(np.ascontiguousarray(cd.A.T)), _lib.ptr(b),
-                                          None, None, None, None, None, C.byref(opt),
-                                          _lib.ptr(np.zeros((B, n))), None,
-                                          _lib.iptr(np.zeros(B, np.int32)), None, None, None, None,
-                                          out)
+            rc = -1 if not args.full else lib.bqp_quadprog_batched(
+                h.value, C.byref(dims), B, C.byref(strides),
+                _lib.ptr(np.ascontiguousarray(cd.H.T)), _lib.ptr(f),
+                _lib.ptr(np.ascontiguousarray(cd.A.T)), _lib.ptr(b),
+                None, None, None, None, None, C.byref(opt),
+                _lib.ptr(np.zeros((B, n))), None,
+                _lib.iptr(np.zeros(B, np.int32)), None, None, None, None,
+                out)
             its = float(np.mean([o.iterations for o in out])) if rc == 0 else None
         except Exception:
             its = None
@@ -1097,10 +1161,11 @@ def bench_aux(args):
                     data=wl['data'],
                     config={'workload': 'C2 problem in quadprog form F1 (bqp.condense), batch %d' % B,
                             'batch_per_gpu': B, 'horizon': 20, 'parallelism': 'dp1'},
-                    roofline=dict(bound='fp64_mfma', achieved=round(ach, 4), peak=78.6,
-                                  unit='TFLOP/s', frac=round(ach / 78.6, 5), kernel_ms=round(kms_mean, 4),
-                                  note='per-iteration flops m n^2 + n^3/3 + 8 m n x the kernel\'s own mean '
-                                       'iteration count (no CPU K_ref for this form)'),
+                    roofline=None if not args.full else dict(
+                        bound='fp64_mfma', achieved=round(ach, 4), peak=78.6,
+                        unit='TFLOP/s', frac=round(ach / 78.6, 5), kernel_ms=round(kms_mean, 4),
+                        note='per-iteration flops m n^2 + n^3/3 + 8 m n x the kernel\'s own mean '
+                             'iteration count (no CPU K_ref for this form)'),
                     cpu_baseline=None,
                     check=dict(converged_frac=float((oe.cpu().numpy() == 1).mean()),
                                iterations_mean=its,
@@ -1124,15 +1189,20 @@ def bench_aux(args):
             r = lb.solve(X0, td, handle=h)
             kms.append(h.kernel_ms()[0])
         el = _t.perf_counter() - t0
-        # CPU leg: the oracle's numpy SQP (interpreted) on the first instances
-        from oracle import lbmpc as olb               # CPU leg only
-        from oracle.mg_model import mg_problem
-        p = olb.f3_problem(mg_problem(), 10, td, g['F_w_N'], g['h_w_N'], g['F_x_d'], g['h_x_d'])
-        ns = min(B, 8)
-        c0 = _t.perf_counter()
-        for i in range(ns):
-            olb.sqp(p, X0[i])
-        cpu = ns / (_t.perf_counter() - c0)
+        outs = {k: r[k] for k in ('z', 'lam', 'cost', 'exitflag')
+                if isinstance(r[k], np.ndarray) and r[k].shape[:1] == (B,)}
+        cpu = None
+        if args.full:
+            # CPU leg: the oracle's numpy SQP (interpreted) on the first instances
+            from oracle import lbmpc as olb               # CPU leg only
+            from oracle.mg_model import mg_problem
+            p = olb.f3_problem(mg_problem(), 10, td, g['F_w_N'], g['h_w_N'], g['F_x_d'], g['h_x_d'])
+            ns = min(B, 8)
+            c0 = _t.perf_counter()
+            for i in range(ns):
+                olb.sqp(p, X0[i])
+            cpu = dict(value=round(ns / (_t.perf_counter() - c0), 2), unit='SQP-solves/s', cores=1,
+                       kind='port', sample='%d solves of oracle/lbmpc.py (numpy)' % ns)
         line = dict(metric='LBMPC SQP solves/s (F3, N=10)', value=round(B * args.steps / el, 2),
                     unit='SQP-solves/s', n_gpus=1, steps=args.steps, warmup=args.warmup,
                     ms_per_step=round(1e3 * el / args.steps, 4), higher_is_better=True,
@@ -1141,10 +1211,11 @@ def bench_aux(args):
                     config={'workload': 'C1: MG LBMPC (F3) N=10, batch %d' % B, 'batch_per_gpu': B,
                             'horizon': 10, 'parallelism': 'dp1'},
                     roofline=None, kernel_ms=round(float(np.mean(kms)), 4),
-                    cpu_baseline=dict(value=round(cpu, 2), unit='SQP-solves/s', cores=1,
-                                      kind='port', sample='%d solves of oracle/lbmpc.py (numpy)' % ns),
+                    cpu_baseline=cpu,
                     check=dict(converged_frac=float((r.exitflag == 1).mean()),
                                mean_sqp_iterations=float(r.iterations.mean())))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs)
     print(json.dumps(line))
 
 

@@ -65,6 +65,53 @@ def test_closed_loop_two_rank_dry_run(cfg):
     assert c['gathered_bytes'] == want
 
 
+@pytest.mark.timeout(240)
+def test_dump_outputs_repeatable_dry_run(tmp_path):
+    """--dump-outputs writes what the last timed step returned as float64 .npy files, the same in
+    every run of the same arguments; a plain run carries no roofline / CPU leg."""
+    import numpy as np
+    import bench
+    dumps = []
+    for name in ('a', 'b'):
+        d = tmp_path / name
+        r = _run('--config', 'C4', '--dry-run', '--batch', '24', '--steps', '2', '--warmup', '1',
+                 '--dump-outputs', str(d))
+        assert r['steps'] == 2 and r['ms_per_step'] > 0
+        assert r['roofline'] is None and r['cpu_baseline'] is None
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ['exitflag.npy', 'u.npy']
+    u, e = bench.StubSolver.moves(bench.workload('C4', 24, 0, 1))
+    assert a['u.npy'].dtype == np.float64 and a['exitflag.npy'].dtype == np.float64
+    assert np.array_equal(a['u.npy'], u) and np.array_equal(a['exitflag.npy'], e)
+    for f in a:
+        assert np.array_equal(a[f], b[f])
+
+
+def test_dump_outputs_cap(tmp_path, monkeypatch):
+    """a set of arrays beyond the cap is cut to one fixed, seeded sample of instances, the same
+    rows of every array, and the files stay within the cap"""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, 'DUMP_CAP_BYTES', 1 << 20)
+    rng = np.random.default_rng(3)
+    arrs = dict(x=rng.standard_normal((5000, 21, 4)), exitflag=np.arange(5000, dtype=np.int32),
+                s=rng.standard_normal(5000).astype(np.float32))
+    out = []
+    for name in ('a', 'b'):
+        d = tmp_path / name
+        bench.dump_outputs(str(d), arrs)
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 1 << 20
+        out.append({f[:-4]: np.load(d / f) for f in os.listdir(d)})
+    a, b = out
+    rows = a['rows'].astype(int)
+    assert 1000 < len(rows) < 5000 and np.all(np.diff(rows) > 0)
+    assert a['s'].dtype == np.float32 and a['x'].dtype == np.float64
+    for k in arrs:
+        assert np.array_equal(a[k], arrs[k][rows]) and np.array_equal(a[k], b[k])
+    assert np.array_equal(a['rows'], b['rows'])
+
+
 def _gather_worker(rank, world, port, q):
     import sys
     import numpy as np
