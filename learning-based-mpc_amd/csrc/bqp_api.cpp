@@ -15,6 +15,9 @@
 
 #include "../../include/bqp.h"
 #include "bqp_internal.h"
+#include "bqp_layout.h"
+
+namespace layout = bqp::layout;
 
 struct DevBuf {
     void* p = nullptr;
@@ -96,10 +99,66 @@ void resolve(const bqp_options* in, bqp_options* o) {
         }                                                                 \
     } while (0)
 
+#define BQP_TRY(x) do { const int _rc = (x); if (_rc) return _rc; } while (0)
+
 // an event owned by an entry point's scope: destroyed on every return (HIP_TRY included)
 struct EventGuard {
     hipEvent_t e = nullptr;
     ~EventGuard() { if (e) hipEventDestroy(e); }
+};
+
+// diagnostic build (make stamps): phase cycle counts per instance in the work buffer
+#ifdef BQP_STAMPS
+constexpr int STAMPS_PER_INSTANCE = 32;
+#else
+constexpr int STAMPS_PER_INSTANCE = 0;
+#endif
+
+layout::Work work_layout(int N, int nv, int mpad, int batch) {
+    return layout::Work(N, nv * nv + 1, nv, mpad, batch, bqp::STATS_W, STAMPS_PER_INSTANCE, bqp::OCP_QUEUES);
+}
+
+// Slack the two solve entry points reserve past their packed staging (16 doubles + 64 bytes):
+// inherited, need unknown (bqp_layout.h keeps the other buffers' slack)
+constexpr size_t STAGE_SOLVE_SLACK = 16 * sizeof(double) + 64;
+
+// Staging of a host-pointer entry point in h->stage: the inputs' device copies, then the outputs',
+// packed in the order they are registered.  Registration takes the address of the pointer that
+// is to hold the device copy; commit() reserves the buffer, sets those pointers and issues the
+// H2D copies on h->stream; finish() copies back the outputs the caller asked for and waits.
+struct Stage : layout::Arena {
+    struct Item { void* slot; const void* src; void* host; layout::Region r; };
+    bqp_handle_s* h;
+    std::vector<Item> items;
+    explicit Stage(bqp_handle_s* h_) : h(h_) { items.reserve(32); }
+    // n elements of src; a null src or n = 0 registers nothing and leaves *dev null.  back: the
+    // call updates the array in place, so it is an output too
+    template <class P, class T>
+    void in(P* dev, const T* src, size_t n, T* back = nullptr) {
+        *dev = nullptr;
+        if (src && n) items.push_back({dev, src, back, take<T>(n)});
+    }
+    // n elements copied to host by finish() unless host is null
+    template <class T>
+    void out(T** dev, size_t n, T* host, size_t align = alignof(T)) {
+        items.push_back({dev, nullptr, host, take_aligned(sizeof(T) * n, align)});
+    }
+    int commit(size_t slack = 0) {
+        HIP_TRY(h->stage.reserve(bytes + slack));
+        for (const Item& e : items) {
+            char* p = (char*)h->stage.p + e.r.off;
+            memcpy(e.slot, &p, sizeof(p));   // *dev = p, whatever *dev points to
+            if (e.src) HIP_TRY(hipMemcpyAsync(p, e.src, e.r.bytes, hipMemcpyHostToDevice, h->stream));
+        }
+        return BQP_OK;
+    }
+    int finish() {
+        for (const Item& e : items)
+            if (e.host && e.r.bytes)
+                HIP_TRY(hipMemcpyAsync(e.host, (char*)h->stage.p + e.r.off, e.r.bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return BQP_OK;
+    }
 };
 
 }  // namespace
@@ -224,8 +283,7 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
                                  double* u, double* theta, double* fval, int* exitflag,
                                  bqp_output* out, const bqp_ocp_duals* duals, void* stream) {
     if (!h) return BQP_E_ARG;
-    int rc = ocp_check(d, batch, D);
-    if (rc) return rc;
+    BQP_TRY(ocp_check(d, batch, D));
     if (!x || !u || !theta || !exitflag) return BQP_E_ARG;
     DevScope ds(h->device);
     hipStream_t st = (hipStream_t)stream;
@@ -297,7 +355,7 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
         // long horizons (N + 1 > 64, two stages per lane) are compiled for <= 256 threads per
         // workgroup: one wave per SIMD, whose 512 registers hold the doubled stage state
         wpb = (N + 1 > 64) ? 2 : 4;
-        // diagnostic (the A/B variants of tools/gpu_r06_*.sh): BQP_OCP_WPB sets the instances per
+        // diagnostic (the A/B library variants of `make ab`): BQP_OCP_WPB sets the instances per
         // workgroup the LDS budget then caps
         if (const char* e = getenv("BQP_OCP_WPB")) {
             const int v = atoi(e);
@@ -309,26 +367,17 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
     int wpb = 1, wpb32 = 1;
     if (!fit_wpb(f32, wpb)) return BQP_E_UNSUPPORTED;
     if (mixed && !fit_wpb(true, wpb32)) return BQP_E_UNSUPPORTED;
-    // workspace: H, Fp, stats
-    const size_t nH = (size_t)(N + 1) * hstride, nF = (size_t)nv * mpad, nS = (size_t)batch * bqp::STATS_W;
-    // + the repair marks (one int per instance, after the stamps of the diagnostic build)
-    const size_t nPol = ((size_t)batch + 1) / 2;
-#ifdef BQP_STAMPS
-    const size_t nStamp = (size_t)batch * 32;
-#else
-    const size_t nStamp = 0;
-#endif
-    // + the work-queue counters of the launches (bqp::OCP_QUEUES ints)
-    const size_t nQ = (bqp::OCP_QUEUES + 1) / 2;
-    HIP_TRY(h->work.reserve(sizeof(double) * (nH + nF + nS + 8 + nStamp + nPol + nQ)));
-    double* Hd = (double*)h->work.p;
-    double* Fd = Hd + nH;
-    double* Sd = Fd + nF;
-    int* polneed = (int*)(Sd + nS + 8 + nStamp);
-    int* queues = (int*)(Sd + nS + 8 + nStamp + nPol);
+    // workspace: H, Fp, stats, the repair marks, the work-queue counters of the launches
+    const layout::Work WL = work_layout(N, nv, mpad, batch);
+    HIP_TRY(h->work.reserve(WL.bytes));
+    double* Hd = layout::at<double>(h->work.p, WL.H);
+    double* Fd = layout::at<double>(h->work.p, WL.F);
+    double* Sd = layout::at<double>(h->work.p, WL.stats);
+    int* polneed = layout::at<int>(h->work.p, WL.marks);
+    int* queues = layout::at<int>(h->work.p, WL.queues);
     const double* Hinst = nullptr;
     if (hinst) {   // per-instance prepared stage-cost tables
-        HIP_TRY(h->wwork.reserve(sizeof(double) * (size_t)batch * nH));
+        HIP_TRY(h->wwork.reserve(sizeof(double) * (size_t)batch * (N + 1) * hstride));
         HIP_TRY(bqp::launch_ocp_prep_h(D->W, D->sW, batch, nx, nu, np, N, hstride, (double*)h->wwork.p, st));
         Hinst = (const double*)h->wwork.p;
     }
@@ -363,7 +412,7 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
         a.lamp_out = duals->lam_p;
     }
 #ifdef BQP_STAMPS
-    a.stamps = Sd + nS + 8;
+    a.stamps = layout::at<double>(h->work.p, WL.stamps);
     h->last_batch = batch;
 #endif
     HIP_TRY(hipEventRecord(h->ev0, st));
@@ -371,12 +420,13 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
         // phase 1: fp32 to the floored tolerances, iterate to the handoff records
         const int hf = bqp::ocp_hand_floats(N, nx, nu, np, mp);
         if (hf <= 0) return BQP_E_UNSUPPORTED;
-        const size_t hrec = ((size_t)hf + 63) & ~(size_t)63;
-        HIP_TRY(h->hwork.reserve(sizeof(float) * hrec * batch + 3 * sizeof(int) * (size_t)batch));
-        float* hb = (float*)h->hwork.p;
-        int* hflag = (int*)(hb + hrec * batch);
-        int* hit = hflag + batch;
-        int* c2flag = hit + batch;    // the continuation's exit flags (diagnostic)
+        const layout::Hwork HL(hf, batch);
+        const size_t hrec = HL.stride;
+        HIP_TRY(h->hwork.reserve(HL.bytes));
+        float* hb = layout::at<float>(h->hwork.p, HL.records);
+        int* hflag = layout::at<int>(h->hwork.p, HL.flags);
+        int* hit = layout::at<int>(h->hwork.p, HL.iters);
+        int* c2flag = layout::at<int>(h->hwork.p, HL.cont);    // the continuation's exit flags (diagnostic)
         h->mixed_flags = hflag;
         h->mixed_cont = c2flag;
         h->mixed_batch = batch;
@@ -419,88 +469,58 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
     return BQP_OK;
 }
 
+// registers the arrays of D with the stage, and nx0 doubles of x0 as the initial states; once
+// st.commit() has run, *Dd is D with the device copies for pointers
+static void stage_ocp_data(Stage& st, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D,
+                           const double* x0, size_t nx0, bqp_ocp_data* Dd) {
+    const size_t nx = d->nx, nu = d->nu, N = d->N, mp = d->n_poly, nv = nx + nu + d->np;
+    *Dd = *D;
+    st.in(&Dd->A, D->A, span(batch, D->sA, nx * nx));
+    st.in(&Dd->B, D->B, span(batch, D->sB, nx * nu));
+    st.in(&Dd->c, D->c, span(batch, D->sc, nx));
+    st.in(&Dd->W, D->W, span(batch, D->sW, (N + 1) * nv * nv));
+    st.in(&Dd->w, D->w, span(batch, D->sw, (N + 1) * nv));
+    st.in(&Dd->xlb, D->xlb, span(batch, D->sxb, (N + 1) * nx));
+    st.in(&Dd->xub, D->xub, span(batch, D->sxb, (N + 1) * nx));
+    st.in(&Dd->ulb, D->ulb, span(batch, D->sub, N * nu));
+    st.in(&Dd->uub, D->uub, span(batch, D->sub, N * nu));
+    st.in(&Dd->Fp, D->Fp, span(batch, D->sFp, mp * nv));
+    st.in(&Dd->hp, D->hp, span(batch, D->shp, mp));
+    st.in(&Dd->x0, x0, nx0);
+}
+
 int bqp_solve_ocp_batched(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D,
                           const bqp_options* opt, double* x, double* u, double* theta,
                           double* fval, int* exitflag, bqp_output* out,
                           const bqp_ocp_duals* duals) {
     if (!h) return BQP_E_ARG;
-    int rc = ocp_check(d, batch, D);
-    if (rc) return rc;
+    BQP_TRY(ocp_check(d, batch, D));
     if (!x || !u || !theta || !exitflag) return BQP_E_ARG;
     DevScope ds(h->device);
-    const int nx = d->nx, nu = d->nu, np = d->np, N = d->N, mp = d->n_poly;
-    const size_t nv = nx + nu + np;
-    // input spans (elements)
-    struct In { const double* src; size_t n; double* dst; };
-    In in[12] = {
-        {D->A, span(batch, D->sA, nx * nx), nullptr},
-        {D->B, span(batch, D->sB, nx * nu), nullptr},
-        {D->c, D->c ? span(batch, D->sc, nx) : 0, nullptr},
-        {D->W, span(batch, D->sW, (N + 1) * nv * nv), nullptr},
-        {D->w, D->w ? span(batch, D->sw, (N + 1) * nv) : 0, nullptr},
-        {D->xlb, D->xlb ? span(batch, D->sxb, (size_t)(N + 1) * nx) : 0, nullptr},
-        {D->xub, D->xub ? span(batch, D->sxb, (size_t)(N + 1) * nx) : 0, nullptr},
-        {D->ulb, D->ulb ? span(batch, D->sub, (size_t)N * nu) : 0, nullptr},
-        {D->uub, D->uub ? span(batch, D->sub, (size_t)N * nu) : 0, nullptr},
-        {D->Fp, mp > 0 ? span(batch, D->sFp, (size_t)mp * nv) : 0, nullptr},
-        {D->hp, mp > 0 ? span(batch, D->shp, (size_t)mp) : 0, nullptr},
-        {D->x0, span(batch, D->sx0, nx), nullptr},
-    };
-    const size_t nxo = (size_t)batch * (N + 1) * nx, nuo = (size_t)batch * N * nu,
-                 nto = (size_t)batch * np, nfo = (size_t)batch;
-    size_t ndual = 0;
-    if (duals) ndual = (size_t)batch * ((size_t)N * nx + (size_t)(N + 1) * nx * 2 + (size_t)N * nu * 2 + mp);
-    size_t total = 0;
-    for (auto& e : in) total += e.n;
-    total += nxo + nuo + nto + nfo + ndual;
-    const size_t outbytes = sizeof(bqp_output) * (size_t)batch;
-    const size_t bytes = sizeof(double) * (total + 16) + sizeof(int) * (size_t)batch + outbytes + 64;
-    HIP_TRY(h->stage.reserve(bytes));
-    double* cur = (double*)h->stage.p;
-    for (auto& e : in) {
-        if (e.n) {
-            e.dst = cur;
-            HIP_TRY(hipMemcpyAsync(cur, e.src, sizeof(double) * e.n, hipMemcpyHostToDevice, h->stream));
-            cur += e.n;
-        }
-    }
-    double* xd = cur; cur += nxo;
-    double* ud = cur; cur += nuo;
-    double* td = cur; cur += nto;
-    double* fd = cur; cur += nfo;
-    double* dual_base = cur; cur += ndual;
-    int* ed = (int*)cur;
-    bqp_output* od = (bqp_output*)(((uintptr_t)(ed + batch) + 63) & ~(uintptr_t)63);
-    bqp_ocp_data Dd = *D;
-    Dd.A = in[0].dst; Dd.B = in[1].dst; Dd.c = in[2].dst; Dd.W = in[3].dst; Dd.w = in[4].dst;
-    Dd.xlb = in[5].dst; Dd.xub = in[6].dst; Dd.ulb = in[7].dst; Dd.uub = in[8].dst;
-    Dd.Fp = in[9].dst; Dd.hp = in[10].dst; Dd.x0 = in[11].dst;
-    bqp_ocp_duals dd;
-    memset(&dd, 0, sizeof(dd));
+    const size_t B = batch, nx = d->nx, nu = d->nu, np = d->np, N = d->N, mp = d->n_poly;
+    Stage st(h);
+    bqp_ocp_data Dd;
+    stage_ocp_data(st, d, batch, D, D->x0, span(batch, D->sx0, nx), &Dd);
+    double *xd, *ud, *td, *fd;
+    int* ed;
+    bqp_output* od;
+    bqp_ocp_duals dd = {};
+    st.out(&xd, B * (N + 1) * nx, x);
+    st.out(&ud, B * N * nu, u);
+    st.out(&td, B * np, theta);
+    st.out(&fd, B, fval);
     if (duals) {
-        double* q = dual_base;
-        dd.pi = q; q += (size_t)batch * N * nx;
-        dd.lam_x = q; q += (size_t)batch * (N + 1) * nx * 2;
-        dd.lam_u = q; q += (size_t)batch * N * nu * 2;
-        dd.lam_p = q;
+        st.out(&dd.pi, B * N * nx, duals->pi);
+        st.out(&dd.lam_x, B * (N + 1) * nx * 2, duals->lam_x);
+        st.out(&dd.lam_u, B * N * nu * 2, duals->lam_u);
+        st.out(&dd.lam_p, B * mp, duals->lam_p);
     }
-    rc = bqp_solve_ocp_batched_device(h, d, batch, &Dd, opt, xd, ud, td, fd, ed,
-                                      out ? od : nullptr, duals ? &dd : nullptr, h->stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(x, xd, sizeof(double) * nxo, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(u, ud, sizeof(double) * nuo, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(theta, td, sizeof(double) * nto, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(exitflag, ed, sizeof(int) * batch, hipMemcpyDeviceToHost, h->stream));
-    if (fval) HIP_TRY(hipMemcpyAsync(fval, fd, sizeof(double) * nfo, hipMemcpyDeviceToHost, h->stream));
-    if (out) HIP_TRY(hipMemcpyAsync(out, od, outbytes, hipMemcpyDeviceToHost, h->stream));
-    if (duals) {
-        if (duals->pi) HIP_TRY(hipMemcpyAsync(duals->pi, dd.pi, sizeof(double) * batch * N * nx, hipMemcpyDeviceToHost, h->stream));
-        if (duals->lam_x) HIP_TRY(hipMemcpyAsync(duals->lam_x, dd.lam_x, sizeof(double) * batch * (N + 1) * nx * 2, hipMemcpyDeviceToHost, h->stream));
-        if (duals->lam_u) HIP_TRY(hipMemcpyAsync(duals->lam_u, dd.lam_u, sizeof(double) * batch * N * nu * 2, hipMemcpyDeviceToHost, h->stream));
-        if (duals->lam_p && mp > 0) HIP_TRY(hipMemcpyAsync(duals->lam_p, dd.lam_p, sizeof(double) * batch * mp, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return BQP_OK;
+    st.out(&ed, B, exitflag);
+    st.out(&od, B, out, 64);
+    BQP_TRY(st.commit(STAGE_SOLVE_SLACK));
+    BQP_TRY(bqp_solve_ocp_batched_device(h, d, batch, &Dd, opt, xd, ud, td, fd, ed, out ? od : nullptr,
+                                         duals ? &dd : nullptr, h->stream));
+    return st.finish();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -521,8 +541,7 @@ int bqp_quadprog_batched_device(bqp_handle h, const bqp_dims* d, int batch, cons
                                 double* lam_eqlin, double* lam_lower, double* lam_upper,
                                 bqp_output* out, void* stream) {
     if (!h) return BQP_E_ARG;
-    int rc = dense_check(d, batch, H, f);
-    if (rc) return rc;
+    BQP_TRY(dense_check(d, batch, H, f));
     if (!x || !exitflag || !s) return BQP_E_ARG;
     if ((d->m > 0 && (!A || !b)) || (d->me > 0 && (!Aeq || !beq))) return BQP_E_ARG;
     DevScope ds(h->device);
@@ -530,9 +549,10 @@ int bqp_quadprog_batched_device(bqp_handle h, const bqp_dims* d, int batch, cons
     bqp_options o;
     resolve(opt, &o);
     const int64_t wst = bqp::dense_work_doubles(d->n, d->m, d->me);
-    HIP_TRY(h->dwork.reserve(sizeof(double) * ((size_t)wst * batch + (size_t)batch * bqp::STATS_W + 8)));
-    double* wk = (double*)h->dwork.p;
-    double* Sd = wk + (size_t)wst * batch;
+    const layout::Dwork DL(wst, batch, bqp::STATS_W);
+    HIP_TRY(h->dwork.reserve(DL.bytes));
+    double* wk = layout::at<double>(h->dwork.p, DL.scratch);
+    double* Sd = layout::at<double>(h->dwork.p, DL.stats);
     bqp::DenseKernelArgs a;
     memset(&a, 0, sizeof(a));
     a.n = d->n; a.m = d->m; a.me = d->me; a.batch = batch; a.max_iter = o.max_iter;
@@ -561,70 +581,58 @@ int bqp_quadprog_batched(bqp_handle h, const bqp_dims* d, int batch, const bqp_s
                          double* lam_lower, double* lam_upper, bqp_output* out) {
     (void)x0;
     if (!h) return BQP_E_ARG;
-    int rc = dense_check(d, batch, H, f);
-    if (rc) return rc;
+    BQP_TRY(dense_check(d, batch, H, f));
     if (!x || !exitflag) return BQP_E_ARG;
-    bqp_strides zs;
-    memset(&zs, 0, sizeof(zs));
+    bqp_strides zs = {};
     if (!s) s = &zs;
     DevScope ds(h->device);
-    const size_t n = d->n, m = d->m, me = d->me;
-    struct In { const double* src; size_t n; double* dst; };
-    In in[8] = {
-        {H, span(batch, s->sH, n * n), nullptr},
-        {f, span(batch, s->sf, n), nullptr},
-        {A, (A && m) ? span(batch, s->sA, m * n) : 0, nullptr},
-        {b, (b && m) ? span(batch, s->sb, m) : 0, nullptr},
-        {Aeq, (Aeq && me) ? span(batch, s->sAeq, me * n) : 0, nullptr},
-        {beq, (beq && me) ? span(batch, s->sbeq, me) : 0, nullptr},
-        {lb, lb ? span(batch, s->slb, n) : 0, nullptr},
-        {ub, ub ? span(batch, s->sub, n) : 0, nullptr},
-    };
-    size_t total = 0;
-    for (auto& e : in) total += e.n;
-    const size_t nxo = (size_t)batch * n, nli = (size_t)batch * m, nle = (size_t)batch * me;
-    total += nxo + batch + nli + nle + 2 * nxo;
-    const size_t outbytes = sizeof(bqp_output) * (size_t)batch;
-    HIP_TRY(h->stage.reserve(sizeof(double) * (total + 16) + sizeof(int) * batch + outbytes + 64));
-    double* cur = (double*)h->stage.p;
-    for (auto& e : in)
-        if (e.n) {
-            e.dst = cur;
-            HIP_TRY(hipMemcpyAsync(cur, e.src, sizeof(double) * e.n, hipMemcpyHostToDevice, h->stream));
-            cur += e.n;
-        }
+    const size_t B = batch, n = d->n, m = d->m, me = d->me;
+    Stage st(h);
+    double *Hd, *xd, *fd, *lid, *led, *lld, *lud;
+    const double *fi, *Ad, *bd, *Aeqd, *beqd, *lbd, *ubd;
+    int* ed;
+    bqp_output* od;
+    st.in(&Hd, H, span(batch, s->sH, n * n));
+    st.in(&fi, f, span(batch, s->sf, n));
+    st.in(&Ad, A, span(batch, s->sA, m * n));
+    st.in(&bd, b, span(batch, s->sb, m));
+    st.in(&Aeqd, Aeq, span(batch, s->sAeq, me * n));
+    st.in(&beqd, beq, span(batch, s->sbeq, me));
+    st.in(&lbd, lb, span(batch, s->slb, n));
+    st.in(&ubd, ub, span(batch, s->sub, n));
+    st.out(&xd, B * n, x);
+    st.out(&fd, B, fval);
+    st.out(&lid, B * m, lam_ineqlin);
+    st.out(&led, B * me, lam_eqlin);
+    st.out(&lld, B * n, lam_lower);
+    st.out(&lud, B * n, lam_upper);
+    st.out(&ed, B, exitflag);
+    st.out(&od, B, out, 64);
+    BQP_TRY(st.commit(STAGE_SOLVE_SLACK));
     // quadprog semantics: the symmetric part of H (a no-op on a symmetric H)
-    HIP_TRY(bqp::launch_dense_symmetrize(in[0].dst, (int)n, s->sH ? batch : 1, s->sH, h->stream));
-    double* xd = cur; cur += nxo;
-    double* fd = cur; cur += batch;
-    double* lid = cur; cur += nli;
-    double* led = cur; cur += nle;
-    double* lld = cur; cur += nxo;
-    double* lud = cur; cur += nxo;
-    int* ed = (int*)cur;
-    bqp_output* od = (bqp_output*)(((uintptr_t)(ed + batch) + 63) & ~(uintptr_t)63);
-    rc = bqp_quadprog_batched_device(h, d, batch, s, in[0].dst, in[1].dst, in[2].dst, in[3].dst,
-                                     in[4].dst, in[5].dst, in[6].dst, in[7].dst, opt, xd, fd, ed,
-                                     lid, led, lld, lud, out ? od : nullptr, h->stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(x, xd, sizeof(double) * nxo, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(exitflag, ed, sizeof(int) * batch, hipMemcpyDeviceToHost, h->stream));
-    if (fval) HIP_TRY(hipMemcpyAsync(fval, fd, sizeof(double) * batch, hipMemcpyDeviceToHost, h->stream));
-    if (lam_ineqlin && m) HIP_TRY(hipMemcpyAsync(lam_ineqlin, lid, sizeof(double) * nli, hipMemcpyDeviceToHost, h->stream));
-    if (lam_eqlin && me) HIP_TRY(hipMemcpyAsync(lam_eqlin, led, sizeof(double) * nle, hipMemcpyDeviceToHost, h->stream));
-    if (lam_lower) HIP_TRY(hipMemcpyAsync(lam_lower, lld, sizeof(double) * nxo, hipMemcpyDeviceToHost, h->stream));
-    if (lam_upper) HIP_TRY(hipMemcpyAsync(lam_upper, lud, sizeof(double) * nxo, hipMemcpyDeviceToHost, h->stream));
-    if (out) HIP_TRY(hipMemcpyAsync(out, od, outbytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return BQP_OK;
+    HIP_TRY(bqp::launch_dense_symmetrize(Hd, (int)n, s->sH ? batch : 1, s->sH, h->stream));
+    BQP_TRY(bqp_quadprog_batched_device(h, d, batch, s, Hd, fi, Ad, bd, Aeqd, beqd, lbd, ubd, opt, xd, fd,
+                                        ed, lid, led, lld, lud, out ? od : nullptr, h->stream));
+    return st.finish();
 }
 
 // ------------------------------------------------------------------------------------------
 // learning-based MPC: Nadaraya-Watson oracle and the Gauss-Newton SQP (bqp_lbmpc.hip)
 // ------------------------------------------------------------------------------------------
-#define LB_NTRIAL 8
+constexpr int LB_NTRIAL = 8;   // line-search trial steps per SQP iteration
 // SQP iterations at one step after which every QP sub-problem is polished (bqp_lbmpc_solve_batched)
 constexpr int LB_POLISH_STALL = 6;
+
+// the NW model's bandwidth and regularisation, oracleL2NW.m's defaults where unset (<= 0)
+static double nw_bandwidth(double v) { return v > 0 ? v : 0.5; }
+static double nw_lambda(double v) { return v > 0 ? v : 1e-3; }
+
+// polish mode of a QP sub-problem (dense kernel) under the SQP's polish option: after 0 / -8 exits
+// (modes 0-2; mode 3: not before the stall), and on every sub-problem (mode 2) once the SQP has
+// stalled, i.e. has run LB_POLISH_STALL iterations at a step
+static int sub_polish(int polish, bool stalled) {
+    return polish < 0 ? 0 : (stalled ? 2 : (polish == 3 ? 0 : 1));
+}
 
 int bqp_nw_oracle_device(bqp_handle h, int batch, int q, const double* data, int64_t sdata,
                          const double* xi, double* g, double* dg, double bandwidth,
@@ -632,8 +640,8 @@ int bqp_nw_oracle_device(bqp_handle h, int batch, int q, const double* data, int
     if (!h || batch <= 0 || q <= 0 || !data || !xi || !g) return BQP_E_ARG;
     if (q > 512) return BQP_E_UNSUPPORTED;
     DevScope ds(h->device);
-    const double bw = bandwidth > 0 ? bandwidth : 0.5, lam = lambda > 0 ? lambda : 1e-3;
-    HIP_TRY(bqp::launch_nw_oracle(batch, q, data, sdata, xi, g, dg, bw, lam, (hipStream_t)stream));
+    HIP_TRY(bqp::launch_nw_oracle(batch, q, data, sdata, xi, g, dg, nw_bandwidth(bandwidth), nw_lambda(lambda),
+                                  (hipStream_t)stream));
     return BQP_OK;
 }
 
@@ -642,21 +650,17 @@ int bqp_nw_oracle(bqp_handle h, int batch, int q, const double* data, int64_t sd
     if (!h || batch <= 0 || q <= 0 || !data || !xi || !g) return BQP_E_ARG;
     if (q > 512) return BQP_E_UNSUPPORTED;
     DevScope ds(h->device);
-    const size_t nd = span(batch, sdata, (size_t)7 * q);
-    const size_t tot = nd + (3 + 4 + 12) * (size_t)batch;
-    HIP_TRY(h->stage.reserve(sizeof(double) * tot));
-    double* dd = (double*)h->stage.p;
-    double* dx = dd + nd;
-    double* dgv = dx + 3 * (size_t)batch;
-    double* ddg = dgv + 4 * (size_t)batch;
-    HIP_TRY(hipMemcpyAsync(dd, data, sizeof(double) * nd, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(dx, xi, sizeof(double) * 3 * batch, hipMemcpyHostToDevice, h->stream));
-    int rc = bqp_nw_oracle_device(h, batch, q, dd, sdata, dx, dgv, ddg, bandwidth, lambda, h->stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(g, dgv, sizeof(double) * 4 * batch, hipMemcpyDeviceToHost, h->stream));
-    if (dg) HIP_TRY(hipMemcpyAsync(dg, ddg, sizeof(double) * 12 * batch, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return BQP_OK;
+    const size_t B = batch;
+    Stage st(h);
+    const double *dd, *dx;
+    double *dgv, *ddg;
+    st.in(&dd, data, span(batch, sdata, (size_t)7 * q));
+    st.in(&dx, xi, 3 * B);
+    st.out(&dgv, 4 * B, g);
+    st.out(&ddg, 12 * B, dg);
+    BQP_TRY(st.commit());
+    BQP_TRY(bqp_nw_oracle_device(h, batch, q, dd, sdata, dx, dgv, ddg, bandwidth, lambda, h->stream));
+    return st.finish();
 }
 
 static int lbmpc_check(const bqp_lbmpc_dims* d, int batch, const bqp_lbmpc_data* D) {
@@ -681,43 +685,38 @@ static hipError_t lbmpc_setup(bqp_handle h, const bqp_lbmpc_dims* d, int batch, 
     const int N = d->N, n = N * d->nu + d->np, m = d->m;
     const int nr = d->n_run * (d->nx + d->nu) + 2 * d->nx;
     const size_t B = batch;
-    const size_t n2 = d->hessian ? B * 3 * (size_t)N * n : 0;   // Jr2, Tr2 of the exact Hessian
-    const size_t nd = B * nr * n + B * nr + B * n * n + B * n + 2 * B * m + B * n + B +
-                      B * LB_NTRIAL + 2 * B + 2 * n2;
-    const size_t ni = 3 * B + 4;
-    hipError_t e = h->lwork.reserve(sizeof(double) * nd + sizeof(int) * ni);
+    const layout::Lwork LL(batch, N, n, nr, m, LB_NTRIAL, d->hessian != 0);
+    hipError_t e = h->lwork.reserve(LL.bytes);
     if (e != hipSuccess) return e;
-    double* p = (double*)h->lwork.p;
+    void* lw = h->lwork.p;
     memset(&a, 0, sizeof(a));
-    a.Jr = p; p += B * nr * n;
-    a.er = p; p += B * nr;
-    a.H = p; p += B * n * n;
-    a.f = p; p += B * n;
-    a.bsh = p; p += B * m;
-    double* lam_int = p; p += B * m;
-    a.d = p; p += B * n;
-    a.cost0 = p; p += B;
-    a.costT = p; p += B * LB_NTRIAL;
-    a.stat = p; p += B;
-    a.cprev = p; p += B;
-    a.Jr2 = p; p += n2;
-    a.Tr2 = p; p += n2;
-    int* ip = (int*)p;
-    a.qpflag = ip; ip += B;
-    a.hused = ip; ip += B;
-    a.done = ip; ip += B;
-    a.ndone = ip;
+    a.Jr = layout::at<double>(lw, LL.Jr);
+    a.er = layout::at<double>(lw, LL.er);
+    a.H = layout::at<double>(lw, LL.H);
+    a.f = layout::at<double>(lw, LL.f);
+    a.bsh = layout::at<double>(lw, LL.bsh);
+    a.d = layout::at<double>(lw, LL.d);
+    a.cost0 = layout::at<double>(lw, LL.cost0);
+    a.costT = layout::at<double>(lw, LL.costT);
+    a.stat = layout::at<double>(lw, LL.stat);
+    a.cprev = layout::at<double>(lw, LL.cprev);
+    a.Jr2 = layout::at<double>(lw, LL.Jr2);
+    a.Tr2 = layout::at<double>(lw, LL.Tr2);
+    a.qpflag = layout::at<int>(lw, LL.qpflag);
+    a.hused = layout::at<int>(lw, LL.hused);
+    a.done = layout::at<int>(lw, LL.done);
+    a.ndone = layout::at<int>(lw, LL.ndone);
     // exact Hessian where its LDS fits (n <= 127), Gauss-Newton otherwise (include/bqp.h)
     a.hess = d->hessian && bqp::lbmpc_hess_fits(n);
-    a.lam = lam ? lam : lam_int;
+    a.lam = lam ? lam : layout::at<double>(lw, LL.lam);
     a.z = z; a.flag = exitflag; a.iters = iterations;
     a.N = N; a.n = n; a.nr = nr; a.m = m; a.q = d->q; a.n_run = d->n_run;
     a.term_learned = d->term_learned; a.batch = batch; a.ntrial = LB_NTRIAL;
     a.wrows = d->mask ? 8 : 7;
     a.max_iter = o.max_iter;
-    const double bw = D->bandwidth > 0 ? D->bandwidth : 0.5;
+    const double bw = nw_bandwidth(D->bandwidth);
     a.hinv2 = 1.0 / (bw * bw);
-    a.lam_nw = D->lambda > 0 ? D->lambda : 1e-3;
+    a.lam_nw = nw_lambda(D->lambda);
     a.tol_step = o.tol_stat;            // |d| <= tol_stat (1 + |z|)
     a.tol_stat = 10.0 * o.tol_stat;     // |grad J + Ain' lam| <= 10 tol_stat (1 + |grad J|)
     a.A = D->A; a.B = D->B; a.K = D->K; a.Lq = D->Lq; a.Lr = D->Lr; a.Lp = D->Lp; a.Lt = D->Lt;
@@ -730,36 +729,96 @@ static hipError_t lbmpc_setup(bqp_handle h, const bqp_lbmpc_dims* d, int batch, 
     if ((e = hipMemsetAsync(a.flag, 0, sizeof(int) * B, st)) != hipSuccess) return e;
     // QP sub-problem (dense kernel): min 0.5 d'Hd + f'd  s.t.  Ain d <= bin - Ain z
     const int64_t wst = bqp::dense_work_doubles(n, m, 0);
-    if ((e = h->dwork.reserve(sizeof(double) * ((size_t)wst * B + B * bqp::STATS_W + 8))) != hipSuccess) return e;
+    const layout::Dwork DL(wst, batch, bqp::STATS_W);
+    if ((e = h->dwork.reserve(DL.bytes)) != hipSuccess) return e;
+    bqp_options qo;
+    bqp_default_options(&qo);
+    qo.max_iter = 100;
     memset(&q, 0, sizeof(q));
-    q.n = n; q.m = m; q.me = 0; q.batch = batch; q.max_iter = 100;
-    q.tol_stat = 1e-8; q.tol_feas = 1e-10; q.tol_comp = 1e-14; q.tau = 0.995;   // bqp_default_options
+    q.n = n; q.m = m; q.me = 0; q.batch = batch; q.max_iter = qo.max_iter;
+    q.tol_stat = qo.tol_stat; q.tol_feas = qo.tol_feas; q.tol_comp = qo.tol_comp; q.tau = qo.tau;
     q.H = a.H; q.f = a.f; q.A = D->Ain; q.b = a.bsh;
     q.sH = (int64_t)n * n; q.sf = n; q.sA = 0; q.sb = m;
     q.x = a.d; q.lam_ineqlin = a.lam; q.exitflag = a.qpflag;
-    q.work = (double*)h->dwork.p; q.work_stride = wst;
-    // sub-problem polish after 0 / -8 exits (modes 0-2; mode 3: not before the stall), and on every
-    // sub-problem (mode 2) once the SQP has run LB_POLISH_STALL iterations at a step: the Gauss-Newton iteration converges linearly on the learned costs of
-    // DMS_LBMPC_casadi.m and interior-point steps accurate to ~1e-8 left it wandering at that level
-    // (tools/diag_dms_gpu.py); with the exact Hessian the SQP ends in 1-4 iterations.  Before the
-    // stall, mode 3 (the closed loop's default) leaves -8 exits unpolished: in the learned loop ~10 %
-    // of the sub-problems end -8 once mu ~ 1e-15 (the factor leaves fp64 range one step past an
-    // accurate iterate, which the update kernel takes as is), and the polish launch for them was
-    // ~1/3 of each SQP iteration (5.5 of 16 ms, BQP_LB_TRACE=2).  A single solve keeps mode 1: its
-    // weakly determined tail inputs move ~1e-6 without the polish.
+    q.work = layout::at<double>(h->dwork.p, DL.scratch); q.work_stride = wst;
+    // The caller sets the sub-problem's polish mode (sub_polish).  Why every sub-problem is polished
+    // once the SQP stalls: the Gauss-Newton iteration converges linearly on the learned costs of
+    // DMS_LBMPC_casadi.m, and interior-point steps accurate to ~1e-8 left it wandering at that
+    // level (tools/diag_dms_gpu.py); with the exact Hessian the SQP ends in 1-4 iterations.  Why
+    // mode 3 (the closed loop's default) leaves -8 exits unpolished before the stall: in the
+    // learned loop ~10 % of the sub-problems end -8 once mu ~ 1e-15 (the factor leaves fp64 range
+    // one step past an accurate iterate, which the update kernel takes as is), and the polish
+    // launch for them was ~1/3 of each SQP iteration (5.5 of 16 ms, BQP_LB_TRACE=2).  A single
+    // solve keeps mode 1: its weakly determined tail inputs move ~1e-6 without the polish.
     // instances whose SQP has finished are not solved again (the update kernel skips them too)
     q.skip = a.done;
-    q.stats = (double*)h->dwork.p + (size_t)wst * B;
+    q.stats = layout::at<double>(h->dwork.p, DL.stats);
     return hipSuccess;
 }
+
+// BQP_LB_TRACE diagnostics of the batched solve's SQP iterations, on stderr: the sub-problems'
+// exit flags per iteration, from 2 on per-launch event times instead.  Both wait for the stream
+// at each iteration; neither launches a kernel.
+struct SqpTrace {
+    const char* env = getenv("BQP_LB_TRACE");
+    const int level = !env ? 0 : (atoi(env) >= 2 ? 2 : 1);   // 0: unset
+    int it = 0;                                              // the SQP iteration being traced
+    EventGuard ev[6];
+    // point k of sqp_iteration: 0 its start, then after rollout, normal (+ hess), dense, trials, update
+    int mark(int k, const bqp::LbmpcArgs& a, hipStream_t st) {
+        if (level == 2) {
+            if (!ev[k].e) HIP_TRY(hipEventCreate(&ev[k].e));
+            HIP_TRY(hipEventRecord(ev[k].e, st));
+            if (k < 5) return BQP_OK;
+            HIP_TRY(hipEventSynchronize(ev[5].e));
+            float ms[5];
+            for (int j = 0; j < 5; ++j) HIP_TRY(hipEventElapsedTime(&ms[j], ev[j].e, ev[j + 1].e));
+            fprintf(stderr, "bqp sqp it %d ms: rollout+sens %.3f normal+hess %.3f dense(+polish) %.3f trials %.3f update %.3f\n",
+                    it, ms[0], ms[1], ms[2], ms[3], ms[4]);
+        } else if (k == 3) {
+            std::vector<int> fl(a.batch), dn(a.batch);
+            HIP_TRY(hipMemcpyAsync(fl.data(), a.qpflag, sizeof(int) * a.batch, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(dn.data(), a.done, sizeof(int) * a.batch, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            int c1 = 0, c0 = 0, c8 = 0, co = 0, act = 0;
+            for (int b = 0; b < a.batch; ++b) {
+                if (dn[b]) continue;
+                ++act;
+                if (fl[b] == 1) ++c1; else if (fl[b] == 0) ++c0; else if (fl[b] == -8) ++c8; else ++co;
+            }
+            fprintf(stderr, "bqp sqp it %d: active %d, sub-problem flags 1:%d 0:%d -8:%d other:%d\n", it, act, c1, c0, c8, co);
+        }
+        return BQP_OK;
+    }
+};
+
+// One SQP iteration of every unfinished instance: rollout with sensitivities, normal equations
+// (+ the exact Hessian), the QP sub-problems, the trial rollouts, the update.  tr: diagnostics of
+// the batched solve, null on the plain path.
+static int sqp_iteration(const bqp::LbmpcArgs& a, const bqp::DenseKernelArgs& q, hipStream_t st,
+                         SqpTrace* tr = nullptr) {
+    if (tr) BQP_TRY(tr->mark(0, a, st));
+    HIP_TRY(bqp::launch_lbmpc_rollout(a, 1, st));
+    if (tr) BQP_TRY(tr->mark(1, a, st));
+    HIP_TRY(bqp::launch_lbmpc_normal(a, st));
+    if (a.hess) HIP_TRY(bqp::launch_lbmpc_hess(a, st));
+    if (tr) BQP_TRY(tr->mark(2, a, st));
+    HIP_TRY(bqp::launch_dense(q, st));
+    if (tr) BQP_TRY(tr->mark(3, a, st));
+    HIP_TRY(bqp::launch_lbmpc_rollout(a, 0, st));
+    if (tr) BQP_TRY(tr->mark(4, a, st));
+    HIP_TRY(bqp::launch_lbmpc_update(a, st));
+    if (tr) BQP_TRY(tr->mark(5, a, st));
+    return BQP_OK;
+}
+static int sqp_iteration_launches(const bqp::LbmpcArgs& a) { return a.hess ? 6 : 5; }
 
 int bqp_lbmpc_solve_batched_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
                                    const bqp_lbmpc_data* D, const bqp_options* opt, double* z,
                                    double* lam, double* cost, int* exitflag, int* iterations,
                                    void* stream) {
     if (!h) return BQP_E_ARG;
-    int rc = lbmpc_check(d, batch, D);
-    if (rc) return rc;
+    BQP_TRY(lbmpc_check(d, batch, D));
     if (!z || !exitflag || !iterations) return BQP_E_ARG;
     DevScope ds(h->device);
     hipStream_t st = (hipStream_t)stream;
@@ -770,56 +829,14 @@ int bqp_lbmpc_solve_batched_device(bqp_handle h, const bqp_lbmpc_dims* d, int ba
     bqp::LbmpcArgs a;
     bqp::DenseKernelArgs q;
     HIP_TRY(lbmpc_setup(h, d, batch, D, o, z, lam, exitflag, iterations, st, a, q));
-    (void)n;
     HIP_TRY(hipEventRecord(h->ev0, st));
     int launches = 0;
-    // diagnostic (BQP_LB_TRACE=2): per-launch event times of the first SQP iterations
-    const char* lbt = getenv("BQP_LB_TRACE");
-    const bool lbt2 = lbt && atoi(lbt) >= 2;
-    EventGuard tg[6];                      // released on every return path
-    hipEvent_t tev[6] = {};
-    if (lbt2)
-        for (int k = 0; k < 6; ++k) { HIP_TRY(hipEventCreate(&tg[k].e)); tev[k] = tg[k].e; }
+    SqpTrace trace;
     for (int it = 0; it < o.max_iter; ++it) {
-        if (lbt2) HIP_TRY(hipEventRecord(tev[0], st));
-        HIP_TRY(bqp::launch_lbmpc_rollout(a, 1, st));
-        if (lbt2) HIP_TRY(hipEventRecord(tev[1], st));
-        HIP_TRY(bqp::launch_lbmpc_normal(a, st));
-        if (a.hess) HIP_TRY(bqp::launch_lbmpc_hess(a, st));
-        if (lbt2) HIP_TRY(hipEventRecord(tev[2], st));
-        q.polish = o.polish < 0 ? 0 : (it >= LB_POLISH_STALL ? 2 : (o.polish == 3 ? 0 : 1));
-        HIP_TRY(bqp::launch_dense(q, st));
-        if (lbt2) {
-            HIP_TRY(hipEventRecord(tev[3], st));
-            HIP_TRY(bqp::launch_lbmpc_rollout(a, 0, st));
-            HIP_TRY(hipEventRecord(tev[4], st));
-            HIP_TRY(bqp::launch_lbmpc_update(a, st));
-            HIP_TRY(hipEventRecord(tev[5], st));
-            HIP_TRY(hipEventSynchronize(tev[5]));
-            float ms[5];
-            for (int k = 0; k < 5; ++k) HIP_TRY(hipEventElapsedTime(&ms[k], tev[k], tev[k + 1]));
-            fprintf(stderr, "bqp sqp it %d ms: rollout+sens %.3f normal+hess %.3f dense(+polish) %.3f trials %.3f update %.3f\n",
-                    it, ms[0], ms[1], ms[2], ms[3], ms[4]);
-        }
-        if (lbt && !lbt2) {     // diagnostic: sub-problem exit flags per SQP iteration
-            std::vector<int> fl(batch), dn(batch);
-            HIP_TRY(hipMemcpyAsync(fl.data(), a.qpflag, sizeof(int) * batch, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(dn.data(), a.done, sizeof(int) * batch, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            int c1 = 0, c0 = 0, c8 = 0, co = 0, act = 0;
-            for (int b = 0; b < batch; ++b) {
-                if (dn[b]) continue;
-                ++act;
-                if (fl[b] == 1) ++c1; else if (fl[b] == 0) ++c0; else if (fl[b] == -8) ++c8; else ++co;
-            }
-            fprintf(stderr, "bqp sqp it %d: active %d, sub-problem flags 1:%d 0:%d -8:%d other:%d\n", it, act,
-                    c1, c0, c8, co);
-        }
-        if (!lbt2) {
-            HIP_TRY(bqp::launch_lbmpc_rollout(a, 0, st));
-            HIP_TRY(bqp::launch_lbmpc_update(a, st));
-        }
-        launches += a.hess ? 6 : 5;
+        trace.it = it;
+        q.polish = sub_polish(o.polish, it >= LB_POLISH_STALL);
+        BQP_TRY(sqp_iteration(a, q, st, trace.level ? &trace : nullptr));
+        launches += sqp_iteration_launches(a);
         // the batch is done when every instance is: polled after each iteration for large
         // sub-problems (an SQP iteration is ~20 ms of kernels at the learned loop's N = 100 shape,
         // and polling every 4th ran up to three iterations past the last instance's convergence),
@@ -838,93 +855,80 @@ int bqp_lbmpc_solve_batched_device(bqp_handle h, const bqp_lbmpc_dims* d, int ba
     return BQP_OK;
 }
 
+// registers the shared model, gain and weight matrices of D with the stage; once st.commit() has
+// run, *Dd is D with their device copies (data, x0, Ain and bin are the caller's to set)
+static void stage_lbmpc_model(Stage& st, const bqp_lbmpc_dims* d, const bqp_lbmpc_data* D, bqp_lbmpc_data* Dd) {
+    const size_t nx = d->nx, nu = d->nu, np = d->np;
+    *Dd = *D;
+    st.in(&Dd->A, D->A, nx * nx);            st.in(&Dd->B, D->B, nx * nu);
+    st.in(&Dd->K, D->K, nu * nx);            st.in(&Dd->Lq, D->Lq, nx * nx);
+    st.in(&Dd->Lr, D->Lr, nu * nu);          st.in(&Dd->Lp, D->Lp, nx * nx);
+    st.in(&Dd->Lt, D->Lt, nx * nx);          st.in(&Dd->LAMBDA, D->LAMBDA, nx * np);
+    st.in(&Dd->PSI, D->PSI, nu * np);        st.in(&Dd->xs, D->xs, nx);
+}
+
 int bqp_lbmpc_solve_batched(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
                             const bqp_lbmpc_data* D, const bqp_options* opt, double* z,
                             double* lam, double* cost, int* exitflag, int* iterations) {
     if (!h) return BQP_E_ARG;
-    int rc = lbmpc_check(d, batch, D);
-    if (rc) return rc;
+    BQP_TRY(lbmpc_check(d, batch, D));
     if (!z || !exitflag || !iterations) return BQP_E_ARG;
     DevScope ds(h->device);
-    const int nx = d->nx, nu = d->nu, np = d->np, N = d->N, m = d->m;
-    const int n = N * nu + np;
-    struct In { const double* src; size_t n; double* dst; };
-    In in[] = {
-        {D->A, (size_t)nx * nx, nullptr}, {D->B, (size_t)nx * nu, nullptr},
-        {D->K, (size_t)nu * nx, nullptr}, {D->Lq, (size_t)nx * nx, nullptr},
-        {D->Lr, (size_t)nu * nu, nullptr}, {D->Lp, (size_t)nx * nx, nullptr},
-        {D->Lt, (size_t)nx * nx, nullptr}, {D->LAMBDA, (size_t)nx * np, nullptr},
-        {D->PSI, (size_t)nu * np, nullptr}, {D->xs, (size_t)nx, nullptr},
-        {D->data, span(batch, D->sdata, (size_t)(d->mask ? 8 : 7) * d->q), nullptr},
-        {D->x0, span(batch, D->sx0, nx), nullptr},
-        {D->Ain, (size_t)m * n, nullptr}, {D->bin, span(batch, D->sbin, m), nullptr},
-        {z, (size_t)batch * n, nullptr},
-    };
-    const int nin = sizeof(in) / sizeof(in[0]);
-    size_t tot = 0;
-    for (int i = 0; i < nin; ++i) tot += (in[i].src ? in[i].n : 0);
-    const size_t nlam = (size_t)batch * m;
-    tot += nlam + batch;
-    HIP_TRY(h->stage.reserve(sizeof(double) * tot + sizeof(int) * 2 * (size_t)batch));
-    double* cur = (double*)h->stage.p;
-    for (int i = 0; i < nin; ++i) {
-        if (!in[i].src || in[i].n == 0) continue;
-        in[i].dst = cur;
-        HIP_TRY(hipMemcpyAsync(cur, in[i].src, sizeof(double) * in[i].n, hipMemcpyHostToDevice, h->stream));
-        cur += in[i].n;
-    }
-    double* zd = in[nin - 1].dst;
-    double* ld = cur; cur += nlam;
-    double* cd = cur; cur += batch;
-    int* ed = (int*)cur;
-    int* itd = ed + batch;
-    bqp_lbmpc_data Dd = *D;
-    Dd.A = in[0].dst; Dd.B = in[1].dst; Dd.K = in[2].dst; Dd.Lq = in[3].dst; Dd.Lr = in[4].dst;
-    Dd.Lp = in[5].dst; Dd.Lt = in[6].dst; Dd.LAMBDA = in[7].dst; Dd.PSI = in[8].dst;
-    Dd.xs = in[9].dst; Dd.data = in[10].dst; Dd.x0 = in[11].dst; Dd.Ain = in[12].dst;
-    Dd.bin = in[13].dst;
-    rc = bqp_lbmpc_solve_batched_device(h, d, batch, &Dd, opt, zd, ld, cd, ed, itd, h->stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(z, zd, sizeof(double) * batch * n, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(exitflag, ed, sizeof(int) * batch, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(iterations, itd, sizeof(int) * batch, hipMemcpyDeviceToHost, h->stream));
-    if (lam && m) HIP_TRY(hipMemcpyAsync(lam, ld, sizeof(double) * nlam, hipMemcpyDeviceToHost, h->stream));
-    if (cost) HIP_TRY(hipMemcpyAsync(cost, cd, sizeof(double) * batch, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return BQP_OK;
+    const size_t B = batch, nx = d->nx, m = d->m, n = (size_t)d->N * d->nu + d->np;
+    Stage st(h);
+    bqp_lbmpc_data Dd;
+    double *zd, *ld, *cd;
+    int *ed, *itd;
+    stage_lbmpc_model(st, d, D, &Dd);
+    st.in(&Dd.data, D->data, span(batch, D->sdata, (size_t)(d->mask ? 8 : 7) * d->q));
+    st.in(&Dd.x0, D->x0, span(batch, D->sx0, nx));
+    st.in(&Dd.Ain, D->Ain, m * n);
+    st.in(&Dd.bin, D->bin, span(batch, D->sbin, m));
+    st.in(&zd, z, B * n, z);   // the initial iterate, and the solution
+    st.out(&ld, B * m, lam);
+    st.out(&cd, B, cost);
+    st.out(&ed, B, exitflag);
+    st.out(&itd, B, iterations);
+    BQP_TRY(st.commit());
+    BQP_TRY(bqp_lbmpc_solve_batched_device(h, d, batch, &Dd, opt, zd, ld, cd, ed, itd, h->stream));
+    return st.finish();
 }
 
 // ------------------------------------------------------------------------------------------
 // closed-loop simulation: batched structured solve + true-plant step, per time step
 // ------------------------------------------------------------------------------------------
+// the loop description of the closed-loop entry points (cl non-null): plant, steps, sampling time
+// and working point; the plants are the Moore-Greitzer model's
+static int loop_check(const bqp_closed_loop* cl, int nx, int nu) {
+    if ((cl->plant != BQP_PLANT_MG_RK4 && cl->plant != BQP_PLANT_MG_ODE23) || cl->steps <= 0 ||
+        !(cl->delta > 0) || !cl->x_eq || !cl->u_eq)
+        return BQP_E_ARG;
+    if (nx != 4 || nu != 1) return BQP_E_UNSUPPORTED;
+    return BQP_OK;
+}
+
 static int closed_loop_impl(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D,
                             const bqp_options* opt, const bqp_closed_loop* cl,
                             const bqp_learning* lw, const double* x_init, double* X, double* U,
                             int* exitflag, void* stream) {
     if (!h || !cl || !x_init || !X || !U) return BQP_E_ARG;
-    int rc = ocp_check(d, batch, D);
-    if (rc) return rc;
-    if ((cl->plant != BQP_PLANT_MG_RK4 && cl->plant != BQP_PLANT_MG_ODE23) || cl->steps <= 0 || !(cl->delta > 0) || !cl->x_eq || !cl->u_eq)
-        return BQP_E_ARG;
-    if (d->nx != 4 || d->nu != 1) return BQP_E_UNSUPPORTED;   // the MG plant
+    BQP_TRY(ocp_check(d, batch, D));
+    BQP_TRY(loop_check(cl, d->nx, d->nu));
     if (lw && (lw->q < 1 || lw->q > (1 << 20) || !lw->XL)) return BQP_E_ARG;
     DevScope ds(h->device);
     hipStream_t st = (hipStream_t)stream;
     const int nx = d->nx, nu = d->nu, np = d->np, N = d->N;
-    const size_t B = batch;
-    const size_t nwin = lw ? B * (size_t)lw->q * 8 : 0;
-    const size_t nd = B * nx + B * (N + 1) * nx + B * N * nu + B * np + nwin;
-    HIP_TRY(h->cwork.reserve(sizeof(double) * nd + sizeof(int) * B));
-    double* s = (double*)h->cwork.p;
-    double* xo = s + B * nx;
-    double* uo = xo + B * (N + 1) * nx;
-    double* th = uo + B * N * nu;
-    double* win = th + B * np;
-    int* fl = (int*)(win + nwin);
+    const layout::CworkOcp CL(batch, nx, nu, np, N, lw ? lw->q : 0);
+    HIP_TRY(h->cwork.reserve(CL.bytes));
+    double* s = layout::at<double>(h->cwork.p, CL.s);
+    double* xo = layout::at<double>(h->cwork.p, CL.x);
+    double* uo = layout::at<double>(h->cwork.p, CL.u);
+    double* th = layout::at<double>(h->cwork.p, CL.theta);
+    double* win = layout::at<double>(h->cwork.p, CL.window);
+    int* fl = layout::at<int>(h->cwork.p, CL.flags);
     if (lw && lw->window) win = lw->window;   // the caller's buffer (device) keeps the final window
     HIP_TRY(bqp::launch_closed_loop_init(batch, nx, cl->steps, x_init, cl->x_eq, s, X, st));
-    const double bw = (lw && lw->bandwidth > 0) ? lw->bandwidth : 0.5;
-    const double lam = (lw && lw->lambda > 0) ? lw->lambda : 1e-3;
+    const double bw = nw_bandwidth(lw ? lw->bandwidth : 0), lam = nw_lambda(lw ? lw->lambda : 0);
     if (lw) HIP_TRY(bqp::launch_lbmpc_window_init(batch, cl->steps, lw->q, lw->mask, x_init, win, lw->XL, st));
     bqp_ocp_data Dm = *D;
     Dm.x0 = s;
@@ -934,9 +938,8 @@ static int closed_loop_impl(bqp_handle h, const bqp_ocp_dims* d, int batch, cons
     HIP_TRY(hipEventRecord(e0.e, st));
     int launches = 0;
     for (int t = 0; t < cl->steps; ++t) {
-        rc = bqp_solve_ocp_batched_device(h, d, batch, &Dm, opt, xo, uo, th, nullptr, fl, nullptr,
-                                          nullptr, stream);
-        if (rc) return rc;
+        BQP_TRY(bqp_solve_ocp_batched_device(h, d, batch, &Dm, opt, xo, uo, th, nullptr, fl, nullptr,
+                                             nullptr, stream));
         launches += h->launches + (lw ? 2 : 1);
         HIP_TRY(bqp::launch_mg_plant(cl->plant, batch, N, cl->steps, t, cl->delta, uo, fl, cl->x_eq, cl->u_eq,
                                      s, X, U, exitflag, st));
@@ -975,72 +978,33 @@ static int closed_loop_host(bqp_handle h, const bqp_ocp_dims* d, int batch, cons
                             int* exitflag) {
     if (!h || !cl || !x_init || !X || !U) return BQP_E_ARG;
     if (lw && (lw->q < 1 || lw->q > (1 << 20) || !lw->XL)) return BQP_E_ARG;
-    int rc = ocp_check(d, batch, D);
-    if (rc) return rc;
+    BQP_TRY(ocp_check(d, batch, D));
     // validate the loop description before sizing the staging buffers from it
-    if ((cl->plant != BQP_PLANT_MG_RK4 && cl->plant != BQP_PLANT_MG_ODE23) || cl->steps <= 0 || !(cl->delta > 0) || !cl->x_eq || !cl->u_eq)
-        return BQP_E_ARG;
-    if (d->nx != 4 || d->nu != 1) return BQP_E_UNSUPPORTED;
+    BQP_TRY(loop_check(cl, d->nx, d->nu));
     DevScope ds(h->device);
-    const int nx = d->nx, nu = d->nu, np = d->np, N = d->N, mp = d->n_poly;
-    const int nv = nx + nu + np;
-    struct In { const double* src; size_t n; double* dst; };
-    In in[] = {
-        {D->A, span(batch, D->sA, (size_t)nx * nx), nullptr},
-        {D->B, span(batch, D->sB, (size_t)nx * nu), nullptr},
-        {D->c, D->c ? span(batch, D->sc, nx) : 0, nullptr},
-        {D->W, span(batch, D->sW, (size_t)(N + 1) * nv * nv), nullptr},
-        {D->w, D->w ? span(batch, D->sw, (size_t)(N + 1) * nv) : 0, nullptr},
-        {D->xlb, D->xlb ? span(batch, D->sxb, (size_t)(N + 1) * nx) : 0, nullptr},
-        {D->xub, D->xub ? span(batch, D->sxb, (size_t)(N + 1) * nx) : 0, nullptr},
-        {D->ulb, D->ulb ? span(batch, D->sub, (size_t)N * nu) : 0, nullptr},
-        {D->uub, D->uub ? span(batch, D->sub, (size_t)N * nu) : 0, nullptr},
-        {D->Fp, mp > 0 ? span(batch, D->sFp, (size_t)mp * nv) : 0, nullptr},
-        {D->hp, mp > 0 ? span(batch, D->shp, mp) : 0, nullptr},
-        {x_init, (size_t)batch * nx, nullptr},
-        {cl->x_eq, (size_t)nx, nullptr},
-        {cl->u_eq, (size_t)nu, nullptr},
-    };
-    const int nin = sizeof(in) / sizeof(in[0]);
-    const size_t nX = (size_t)batch * (cl->steps + 1) * nx, nU = (size_t)batch * cl->steps * nu;
-    const size_t nW = lw ? (size_t)batch * lw->q * 8 : 0;
-    size_t tot = nX + nU + (lw ? nX + nW : 0);
-    for (int i = 0; i < nin; ++i) tot += (in[i].src ? in[i].n : 0);
-    HIP_TRY(h->stage.reserve(sizeof(double) * tot + sizeof(int) * (size_t)batch * cl->steps));
-    double* cur = (double*)h->stage.p;
-    for (int i = 0; i < nin; ++i) {
-        if (!in[i].src || in[i].n == 0) continue;
-        in[i].dst = cur;
-        HIP_TRY(hipMemcpyAsync(cur, in[i].src, sizeof(double) * in[i].n, hipMemcpyHostToDevice, h->stream));
-        cur += in[i].n;
-    }
-    double* Xd = cur; cur += nX;
-    double* Ud = cur; cur += nU;
-    double* XLd = nullptr;
-    double* Wd = nullptr;
-    if (lw) { XLd = cur; cur += nX; Wd = cur; cur += nW; }
-    int* Fd = (int*)cur;
-    bqp_ocp_data Dd = *D;
-    Dd.A = in[0].dst; Dd.B = in[1].dst; Dd.c = in[2].dst; Dd.W = in[3].dst; Dd.w = in[4].dst;
-    Dd.xlb = in[5].dst; Dd.xub = in[6].dst; Dd.ulb = in[7].dst; Dd.uub = in[8].dst;
-    Dd.Fp = in[9].dst; Dd.hp = in[10].dst;
-    Dd.x0 = in[11].dst;   // placeholder (the loop feeds the measured states)
+    const size_t B = batch, S = cl->steps, nx = d->nx, nu = d->nu;
+    const size_t nX = B * (S + 1) * nx;
+    Stage st(h);
+    bqp_ocp_data Dd;
     bqp_closed_loop cd = *cl;
-    cd.x_eq = in[12].dst; cd.u_eq = in[13].dst;
-    bqp_learning ld;
-    if (lw) { ld = *lw; ld.XL = XLd; ld.window = Wd; }
-    rc = closed_loop_impl(h, d, batch, &Dd, opt, &cd, lw ? &ld : nullptr, in[11].dst, Xd, Ud,
-                          exitflag ? Fd : nullptr, h->stream);
-    if (rc) return rc;
+    bqp_learning ld = lw ? *lw : bqp_learning{};
+    double *Xd, *Ud;
+    int* Fd;
+    // Dd.x0: the initial states (a placeholder: the loop feeds the measured states)
+    stage_ocp_data(st, d, batch, D, x_init, B * nx, &Dd);
+    st.in(&cd.x_eq, cl->x_eq, nx);
+    st.in(&cd.u_eq, cl->u_eq, nu);
+    st.out(&Xd, nX, X);
+    st.out(&Ud, B * S * nu, U);
     if (lw) {
-        HIP_TRY(hipMemcpyAsync(lw->XL, XLd, sizeof(double) * nX, hipMemcpyDeviceToHost, h->stream));
-        if (lw->window) HIP_TRY(hipMemcpyAsync(lw->window, Wd, sizeof(double) * nW, hipMemcpyDeviceToHost, h->stream));
+        st.out(&ld.XL, nX, lw->XL);
+        st.out(&ld.window, B * lw->q * 8, lw->window);
     }
-    HIP_TRY(hipMemcpyAsync(X, Xd, sizeof(double) * nX, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(U, Ud, sizeof(double) * nU, hipMemcpyDeviceToHost, h->stream));
-    if (exitflag) HIP_TRY(hipMemcpyAsync(exitflag, Fd, sizeof(int) * (size_t)batch * cl->steps, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return BQP_OK;
+    st.out(&Fd, B * S, exitflag);
+    BQP_TRY(st.commit());
+    BQP_TRY(closed_loop_impl(h, d, batch, &Dd, opt, &cd, lw ? &ld : nullptr, Dd.x0, Xd, Ud,
+                             exitflag ? Fd : nullptr, h->stream));
+    return st.finish();
 }
 
 int bqp_closed_loop_ocp(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D,
@@ -1065,9 +1029,7 @@ static int sqp_loop_check(const bqp_lbmpc_dims* d, int batch, const bqp_lbmpc_da
                           const bqp_learning* lw, const double* x_init, const double* X,
                           const double* U) {
     if (!d || !D || !sl || !cl || !lw || !x_init || !X || !U || batch <= 0) return BQP_E_ARG;
-    if ((cl->plant != BQP_PLANT_MG_RK4 && cl->plant != BQP_PLANT_MG_ODE23) || cl->steps <= 0 || !(cl->delta > 0) || !cl->x_eq || !cl->u_eq)
-        return BQP_E_ARG;
-    if (d->nx != 4 || d->nu != 1) return BQP_E_UNSUPPORTED;   // the MG plant
+    BQP_TRY(loop_check(cl, d->nx, d->nu));
     if (lw->q != d->q || !lw->XL || (lw->mask != 0 && lw->mask != 1)) return BQP_E_ARG;
     if (d->m > 0 && (!sl->bin0 || !sl->Bx)) return BQP_E_ARG;
     // the loop supplies the window, the measured state and the rhs: check the rest
@@ -1085,22 +1047,21 @@ int bqp_closed_loop_sqp_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
                                const bqp_learning* lw, const double* x_init, double* X, double* U,
                                int* exitflag, void* stream) {
     if (!h) return BQP_E_ARG;
-    int rc = sqp_loop_check(d, batch, D, sl, cl, lw, x_init, X, U);
-    if (rc) return rc;
+    BQP_TRY(sqp_loop_check(d, batch, D, sl, cl, lw, x_init, X, U));
     DevScope ds(h->device);
     hipStream_t st = (hipStream_t)stream;
     const int nx = d->nx, N = d->N, m = d->m, q = d->q;
     const int n = N * d->nu + d->np;
     const size_t B = batch;
-    const size_t nd = B * nx + B * n + B * m + B + B * (size_t)q * 8;
-    HIP_TRY(h->cwork.reserve(sizeof(double) * nd + sizeof(int) * (3 * B + 2)));
-    double* s = (double*)h->cwork.p;     // measured deviation state
-    double* z = s + B * nx;               // SQP iterate / solution
-    double* bin = z + B * n;              // rhs of the step's constraints
-    double* uo = bin + B * m;             // first input (deviation)
-    double* win = uo + B;                 // window ring, 8 doubles per point
-    int* fl = (int*)(win + B * (size_t)q * 8);
-    int* it = fl + B;
+    const layout::CworkSqp CL(batch, nx, n, m, q);
+    HIP_TRY(h->cwork.reserve(CL.bytes));
+    double* s = layout::at<double>(h->cwork.p, CL.s);         // measured deviation state
+    double* z = layout::at<double>(h->cwork.p, CL.z);         // SQP iterate / solution
+    double* bin = layout::at<double>(h->cwork.p, CL.bin);     // rhs of the step's constraints
+    double* uo = layout::at<double>(h->cwork.p, CL.u0);       // first input (deviation)
+    double* win = layout::at<double>(h->cwork.p, CL.window);  // window ring, 8 doubles per point
+    int* fl = layout::at<int>(h->cwork.p, CL.flags);
+    int* it = layout::at<int>(h->cwork.p, CL.iters);
     if (lw->window) win = lw->window;
     bqp_options ol;                       // the loop's default polish: only once the SQP stalls
     resolve(opt, &ol);
@@ -1110,9 +1071,9 @@ int bqp_closed_loop_sqp_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
     HIP_TRY(bqp::launch_lbmpc_window_init(batch, cl->steps, q, lw->mask, x_init, win, lw->XL, st));
     HIP_TRY(hipMemsetAsync(z, 0, sizeof(double) * B * n, st));
     // the learned model's NW parameters: the loop's (bqp_learning) when set, else the model's own
-    // (bqp_lbmpc_data, oracleL2NW.m: h = 0.5, lambda = 1e-3 when both are unset)
-    const double bw = lw->bandwidth > 0 ? lw->bandwidth : (D->bandwidth > 0 ? D->bandwidth : 0.5);
-    const double lam = lw->lambda > 0 ? lw->lambda : (D->lambda > 0 ? D->lambda : 1e-3);
+    // (bqp_lbmpc_data), else the defaults
+    const double bw = nw_bandwidth(lw->bandwidth > 0 ? lw->bandwidth : D->bandwidth);
+    const double lam = nw_lambda(lw->lambda > 0 ? lw->lambda : D->lambda);
     bqp_lbmpc_dims dl = *d;
     dl.mask = 1;                          // the loop's window always carries the validity row
     bqp_lbmpc_data Dl = *D;
@@ -1135,16 +1096,16 @@ int bqp_closed_loop_sqp_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
         // batch's slowest instance had converged (2.4 SQP iterations per step on average against
         // up to 6 at a step) while the converged ones idled; per instance the two forms do the
         // same operations in the same order (tests/test_gpu_lbmpc_dms.py compares them).
-        int* ts = it + B;
-        int* nfin = ts + B;
-        HIP_TRY(hipMemsetAsync(ts, 0, sizeof(int) * (B + 1), st));
+        int* ts = layout::at<int>(h->cwork.p, CL.ts);
+        int* nfin = layout::at<int>(h->cwork.p, CL.nfin);
+        HIP_TRY(hipMemsetAsync(ts, 0, sizeof(int) * (B + 1), st));   // ts[], nfin
         HIP_TRY(bqp::launch_sqp_loop_prep(batch, nx, n, m, N * d->nu, 0, s, sl->bin0, sl->Bx, bin, z, st));
         bqp::LbmpcArgs a;
         bqp::DenseKernelArgs qd;
         HIP_TRY(lbmpc_setup(h, &dl, batch, &Dl, *opt, z, nullptr, fl, it, st, a, qd));
         // sub-problem polish per instance: from its own SQP iteration count (lbmpc solve: mode 2
         // from LB_POLISH_STALL on, before it the loop's mode 3 - none - or 1)
-        qd.polish = opt->polish < 0 ? 0 : (opt->polish == 3 ? 0 : 1);
+        qd.polish = sub_polish(opt->polish, false);
         qd.pol_it = opt->polish < 0 ? nullptr : a.iters;
         qd.pol_stall = LB_POLISH_STALL;
         bqp::SqpAdvanceArgs v;
@@ -1159,14 +1120,9 @@ int bqp_closed_loop_sqp_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
         v.flags = exitflag; v.itlog = sl->iterations;
         const int max_rounds = cl->steps * opt->max_iter;
         for (int r = 0; r < max_rounds; ++r) {
-            HIP_TRY(bqp::launch_lbmpc_rollout(a, 1, st));
-            HIP_TRY(bqp::launch_lbmpc_normal(a, st));
-            if (a.hess) HIP_TRY(bqp::launch_lbmpc_hess(a, st));
-            HIP_TRY(bqp::launch_dense(qd, st));
-            HIP_TRY(bqp::launch_lbmpc_rollout(a, 0, st));
-            HIP_TRY(bqp::launch_lbmpc_update(a, st));
+            BQP_TRY(sqp_iteration(a, qd, st));
             HIP_TRY(bqp::launch_sqp_loop_advance(v, st));
-            launches += a.hess ? 7 : 6;
+            launches += sqp_iteration_launches(a) + 1;
             int nf = 0;
             HIP_TRY(hipMemcpyAsync(&nf, nfin, sizeof(int), hipMemcpyDeviceToHost, st));
             HIP_TRY(hipStreamSynchronize(st));
@@ -1177,9 +1133,8 @@ int bqp_closed_loop_sqp_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
         HIP_TRY(bqp::launch_sqp_loop_prep(batch, nx, n, m, N * d->nu, t > 0 && sl->warm, s,
                                           sl->bin0, sl->Bx, bin, z, st));
         if (t > 0 && !sl->warm) HIP_TRY(hipMemsetAsync(z, 0, sizeof(double) * B * n, st));
-        rc = bqp_lbmpc_solve_batched_device(h, &dl, batch, &Dl, opt, z, nullptr, nullptr, fl, it,
-                                            stream);
-        if (rc) return rc;
+        BQP_TRY(bqp_lbmpc_solve_batched_device(h, &dl, batch, &Dl, opt, z, nullptr, nullptr, fl, it,
+                                               stream));
         launches += h->launches;
         HIP_TRY(bqp::launch_sqp_loop_u0(batch, nx, n, D->K, s, z, uo, it, cl->steps, t,
                                         sl->Z, sl->iterations, st));
@@ -1202,66 +1157,38 @@ int bqp_closed_loop_sqp(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
                         const bqp_closed_loop* cl, const bqp_learning* lw, const double* x_init,
                         double* X, double* U, int* exitflag) {
     if (!h) return BQP_E_ARG;
-    int rc = sqp_loop_check(d, batch, D, sl, cl, lw, x_init, X, U);
-    if (rc) return rc;
+    BQP_TRY(sqp_loop_check(d, batch, D, sl, cl, lw, x_init, X, U));
     DevScope ds(h->device);
-    const int nx = d->nx, nu = d->nu, np = d->np, N = d->N, m = d->m, q = d->q;
-    const int n = N * nu + np;
-    struct In { const double* src; size_t n; double* dst; };
-    In in[] = {
-        {D->A, (size_t)nx * nx, nullptr}, {D->B, (size_t)nx * nu, nullptr},
-        {D->K, (size_t)nu * nx, nullptr}, {D->Lq, (size_t)nx * nx, nullptr},
-        {D->Lr, (size_t)nu * nu, nullptr}, {D->Lp, (size_t)nx * nx, nullptr},
-        {D->Lt, (size_t)nx * nx, nullptr}, {D->LAMBDA, (size_t)nx * np, nullptr},
-        {D->PSI, (size_t)nu * np, nullptr}, {D->xs, (size_t)nx, nullptr},
-        {D->Ain, (size_t)m * n, nullptr}, {sl->bin0, (size_t)m, nullptr},
-        {sl->Bx, (size_t)m * nx, nullptr}, {x_init, (size_t)batch * nx, nullptr},
-        {cl->x_eq, (size_t)nx, nullptr}, {cl->u_eq, (size_t)nu, nullptr},
-    };
-    const int nin = sizeof(in) / sizeof(in[0]);
-    const size_t B = batch, S = cl->steps;
-    const size_t nX = B * (S + 1) * nx, nU = B * S * nu, nW = B * (size_t)q * 8, nZ = B * S * n;
-    size_t tot = 2 * nX + nU + nW + (sl->Z ? nZ : 0);
-    for (int i = 0; i < nin; ++i) tot += (in[i].src ? in[i].n : 0);
-    HIP_TRY(h->stage.reserve(sizeof(double) * tot + sizeof(int) * 2 * B * S));
-    double* cur = (double*)h->stage.p;
-    for (int i = 0; i < nin; ++i) {
-        if (!in[i].src || in[i].n == 0) continue;
-        in[i].dst = cur;
-        HIP_TRY(hipMemcpyAsync(cur, in[i].src, sizeof(double) * in[i].n, hipMemcpyHostToDevice, h->stream));
-        cur += in[i].n;
-    }
-    double* Xd = cur; cur += nX;
-    double* Ud = cur; cur += nU;
-    double* XLd = cur; cur += nX;
-    double* Wd = cur; cur += nW;
-    double* Zd = nullptr;
-    if (sl->Z) { Zd = cur; cur += nZ; }
-    int* Fd = (int*)cur;
-    int* Id = Fd + B * S;
-    bqp_lbmpc_data Dd = *D;
-    Dd.A = in[0].dst; Dd.B = in[1].dst; Dd.K = in[2].dst; Dd.Lq = in[3].dst; Dd.Lr = in[4].dst;
-    Dd.Lp = in[5].dst; Dd.Lt = in[6].dst; Dd.LAMBDA = in[7].dst; Dd.PSI = in[8].dst;
-    Dd.xs = in[9].dst; Dd.Ain = in[10].dst;
+    const size_t B = batch, S = cl->steps, nx = d->nx, nu = d->nu, m = d->m, q = d->q;
+    const size_t n = (size_t)d->N * nu + d->np;
+    const size_t nX = B * (S + 1) * nx;
+    Stage st(h);
+    bqp_lbmpc_data Dd;
     bqp_sqp_loop sd = *sl;
-    sd.bin0 = in[11].dst; sd.Bx = in[12].dst;
-    sd.Z = Zd; sd.iterations = sl->iterations ? Id : nullptr;
     bqp_closed_loop cd = *cl;
-    cd.x_eq = in[14].dst; cd.u_eq = in[15].dst;
     bqp_learning ld = *lw;
-    ld.XL = XLd; ld.window = Wd;
-    rc = bqp_closed_loop_sqp_device(h, d, batch, &Dd, &sd, opt, &cd, &ld, in[13].dst, Xd, Ud,
-                                    exitflag ? Fd : nullptr, h->stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(X, Xd, sizeof(double) * nX, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(U, Ud, sizeof(double) * nU, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipMemcpyAsync(lw->XL, XLd, sizeof(double) * nX, hipMemcpyDeviceToHost, h->stream));
-    if (lw->window) HIP_TRY(hipMemcpyAsync(lw->window, Wd, sizeof(double) * nW, hipMemcpyDeviceToHost, h->stream));
-    if (sl->Z) HIP_TRY(hipMemcpyAsync(sl->Z, Zd, sizeof(double) * nZ, hipMemcpyDeviceToHost, h->stream));
-    if (exitflag) HIP_TRY(hipMemcpyAsync(exitflag, Fd, sizeof(int) * B * S, hipMemcpyDeviceToHost, h->stream));
-    if (sl->iterations) HIP_TRY(hipMemcpyAsync(sl->iterations, Id, sizeof(int) * B * S, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    return BQP_OK;
+    const double* xi;
+    double *Xd, *Ud;
+    int *Fd, *Id;
+    stage_lbmpc_model(st, d, D, &Dd);
+    st.in(&Dd.Ain, D->Ain, m * n);
+    st.in(&sd.bin0, sl->bin0, m);
+    st.in(&sd.Bx, sl->Bx, m * nx);
+    st.in(&xi, x_init, B * nx);
+    st.in(&cd.x_eq, cl->x_eq, nx);
+    st.in(&cd.u_eq, cl->u_eq, nu);
+    st.out(&Xd, nX, X);
+    st.out(&Ud, B * S * nu, U);
+    st.out(&ld.XL, nX, lw->XL);
+    st.out(&ld.window, B * q * 8, lw->window);
+    if (sl->Z) st.out(&sd.Z, B * S * n, sl->Z);
+    st.out(&Fd, B * S, exitflag);
+    st.out(&Id, B * S, sl->iterations);
+    BQP_TRY(st.commit());
+    sd.iterations = sl->iterations ? Id : nullptr;
+    BQP_TRY(bqp_closed_loop_sqp_device(h, d, batch, &Dd, &sd, opt, &cd, &ld, xi, Xd, Ud,
+                                       exitflag ? Fd : nullptr, h->stream));
+    return st.finish();
 }
 
 #ifdef BQP_STAMPS
@@ -1270,12 +1197,11 @@ int bqp_closed_loop_sqp(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
 int bqp_debug_stamps(bqp_handle h, int N, int nv, int mp, double* out) {
     if (!h || !out) return BQP_E_ARG;
     DevScope ds(h->device);
-    const int hstride = nv * nv + 1;
     const int mpad = 64 * bqp::ocp_rpl_for(std::max(mp, 1));
-    const size_t off = (size_t)(N + 1) * hstride + (size_t)nv * mpad + (size_t)h->last_batch * bqp::STATS_W + 8;
+    const layout::Work WL = work_layout(N, nv, mpad, h->last_batch);
     HIP_TRY(hipStreamSynchronize(h->stream));
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, (double*)h->work.p + off, sizeof(double) * h->last_batch * 32, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, layout::at<double>(h->work.p, WL.stamps), WL.stamps.bytes, hipMemcpyDeviceToHost));
     return BQP_OK;
 }
 #endif
