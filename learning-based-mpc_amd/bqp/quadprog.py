@@ -104,7 +104,8 @@ def quadprog(H, f, A=None, b=None, Aeq=None, beq=None, lb=None, ub=None, x0=None
     _lib.check(rc, 'bqp_quadprog_batched')
     output = dict(iterations=np.array([q.iterations for q in out]),
                   constrviolation=np.array([q.constrviolation for q in out]),
-                  firstorderopt=np.array([q.firstorderopt for q in out]))
+                  firstorderopt=np.array([q.firstorderopt for q in out]),
+                  polished=np.array([q.polished for q in out]))
     lam = dict(ineqlin=li[:, :m], eqlin=le[:, :me], lower=ll, upper=lu)
     if fixinfo is not None:
         idx, me0 = fixinfo

@@ -123,7 +123,7 @@ def test_dense_lds_layout_sizes(n, handle):
 @pytest.mark.parametrize('m', [300, 1024])
 def test_dense_rows_in_registers_equals_workspace_form(m, handle):
     """round 6: dense_ipm_kernel keeps the row state of A's rows in registers and the n-vectors in
-    LDS when they fit (m <= 1024, n <= 106: the learned loop's sub-problem is n = 101, m = 1024);
+    LDS when they fit (m <= 1024, n <= 101: the learned loop's sub-problem is n = 101, m = 1024);
     BQP_DENSE_NO_RG=1 selects the workspace form of the same iteration.  The two are compiled
     separately and are not bit-identical (a product with two uses, e.g. t lam in the residual
     pass, is fused into an FMA where the workspace form re-loads its operands and kept where the
@@ -131,7 +131,8 @@ def test_dense_rows_in_registers_equals_workspace_form(m, handle):
     active) round-off moves the iteration count (tools/diag_dense_rg.py: 18 / 16 and 18 / 35
     iterations, each form deterministic run to run): both converge, to the same optimum (x within
     1e-8, f within 1e-9 relative), each run of the register form repeats bit for bit, KKT
-    stationarity holds, and for m = 300 the result is the exact optimum (oracle/exact_qp.py)."""
+    stationarity holds, and at both m the result of either form is the exact optimum
+    (oracle/exact_qp.py)."""
     import os
     import bqp
     from oracle import exact_qp
@@ -158,10 +159,13 @@ def test_dense_rows_in_registers_equals_workspace_form(m, handle):
     for i in range(B):
         r = H @ x[i] + f[i] + A.T @ lam['ineqlin'][i] + lam['upper'][i] - lam['lower'][i]
         assert np.abs(r).max() < 1e-6 * (1 + np.abs(f[i]).max())
-    if m == 300:
-        A2 = np.vstack([A, np.eye(n), -np.eye(n)])
-        z = exact_qp.solve(H, f[0], A2, np.concatenate([b[0], ub, -lb]))["z"]
-        assert np.abs(x[0] - z).max() / max(1, np.abs(z).max()) < 5e-8
+    # the exact optimum at both m (exact_qp solves the 1226-row problem of m = 1024 in under a
+    # second on the CPU); tests/test_gpu_quadprog_planted.py pins the same shape, in both
+    # compilations, to a planted optimum with known multipliers
+    A2 = np.vstack([A, np.eye(n), -np.eye(n)])
+    z = exact_qp.solve(H, f[0], A2, np.concatenate([b[0], ub, -lb]))["z"]
+    assert np.abs(x[0] - z).max() / max(1, np.abs(z).max()) < 5e-8
+    assert np.abs(xw[0] - z).max() / max(1, np.abs(z).max()) < 5e-8
 
 
 def test_nonsymmetric_h_uses_symmetric_part(handle):
