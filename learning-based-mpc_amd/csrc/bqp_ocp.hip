@@ -29,6 +29,7 @@
 #include <stdlib.h>
 
 #include "bqp_internal.h"
+#include "bqp_lanes.h"
 #include "bqp_wave.h"
 
 namespace bqp {
@@ -133,6 +134,15 @@ __device__ __forceinline__ int opq_s(int v) {
 // fused multiply-add in the instantiation's precision (no promotion of the fp32 path to fp64)
 __device__ __forceinline__ double fmar(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float fmar(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// acc += a * b in the stage wave's per-stage passes.  fp64: left to hipcc's contraction, which fuses
+// every one of them (no packed fp64 multiply exists).  fp32: written as one fma - left to the
+// compiler, neighbouring entries' products are paired into v_pk_mul_f32 with separate adds, so
+// which products are fused follows how a pass deals its entries out over lanes (stage_wave's G)
+#ifdef BQP_F32
+#define MADD(acc, a, b) acc = fmar((a), (b), (acc))
+#else
+#define MADD(acc, a, b) acc += (a) * (b)
+#endif
 
 // Factor of a small SPD block for chol_solve_small (R^_k = M_uu per stage in the Riccati
 // recursion, P_0[theta, theta] once per factorisation).  n = 2 (the DI model family): LDL' with
@@ -355,7 +365,15 @@ __device__ __forceinline__ bool hand_warm(const OcpKernelArgs& a, int inst) {
 // ==========================================================================================
 // stage wave
 // ==========================================================================================
-template <int NX, int NU, int NP, int SPL, bool POL>
+// G: lane groups (bqp_lanes.h).  G = 1: lane k owns stage k.  G > 1 (short horizons, G (N + 1) <=
+// 64): the lanes k + g (N + 1) serve stage k.  Each of them keeps the stage's whole iterate in
+// registers and applies the same updates to it (bit-equal copies), and in the per-stage passes
+// whose cost is their per-lane instruction count (stage_partials, prep_iter, the right-
+// hand side and pre-pass of solve, post-backward) forms only its ES = ceil(NS / G) entries of the
+// s part, by the operation sequence the entry has at G = 1.  A pass that reads a whole stage
+// vector another pass produced by entries reads it from LDS after a wave_sync or a barrier; a
+// pass that reads back its own entries needs neither.
+template <int NX, int NU, int NP, int SPL, bool POL, int G>
 __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, const QpLds& L,
                                            const real* Hs, int lane_w, int inst, int pslot) {
     const int lane = lane_w;
@@ -364,7 +382,14 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     constexpr int NS = NX + NP;
     constexpr int NV = NS + NU;
     constexpr int NB = NX + NU;
+    static_assert(G == 1 || (SPL == 1 && lanes::compiled(NS, NU, G)), "lane groups: short horizons only");
+    constexpr int ES = lanes::entries_per_lane(NS, G);   // s-part entries per lane
     const int N = a.N, kp = a.kp, hstride = a.hstride;
+    // the stage a lane serves (> N: none); j: second stage of the lane at SPL = 2
+    auto stage_of = [&](int ln, int j) __attribute__((always_inline)) -> int {
+        if constexpr (G > 1) return lanes::stage_lane(ln, N, G).k;
+        else return ln + WAVE * j;
+    };
     real* X = W + L.xch;
     STAMP_DECL;
     constexpr bool LNG = BQP_LNG_OK && SPL == 2;     // long-horizon layout (QpLds lng)
@@ -425,7 +450,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     for (int i = 0; i < NX; ++i) x0max = fmax(x0max, fabs(x0[i]));
 #pragma unroll
     for (int j = 0; j < SPL; ++j) {
-        const int k = lane + WAVE * j;
+        const int k = stage_of(lane, j);
 #pragma unroll
         for (int i = 0; i < NS; ++i) { s[j][i] = 0.0; pi[j][i] = 0.0; }
 #pragma unroll
@@ -441,7 +466,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         const int lane = opq(lane_w);
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k <= N) {
 #pragma unroll
                 for (int i = 0; i < NS; ++i) { W[L.xs + k * NS + i] = s[j][i]; W[L.qt_xpi + k * NS + i] = pi[j][i]; }
@@ -457,9 +482,70 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     auto stage_partials = [&](real& feasA, real& gsA) __attribute__((always_inline)) {
         const int lane = opq(lane_w);
         real fe = 0, gs = 0;
+        if constexpr (G > 1) {
+            // lane (k, g): its ES entries of g, rs and re, the u part on every lane of the stage;
+            // the entry of pi_k from its LDS copy (write_state precedes every call)
+            const lanes::StageLane sl = lanes::stage_lane(lane, N, G);
+            const int k = sl.k;
+            if (k <= N) {
+                BQP_HK(k);
+                real v[NV], pn[NS], gu[NU];
+#pragma unroll
+                for (int i = 0; i < NS; ++i) v[i] = s[0][i];
+#pragma unroll
+                for (int i = 0; i < NU; ++i) v[NS + i] = (k < N) ? u[0][i] : 0.0;
+#pragma unroll
+                for (int i = 0; i < NS; ++i) pn[i] = (k < N) ? W[L.qt_xpi + (k + 1) * NS + i] : 0.0;
+#pragma unroll
+                for (int t = 0; t < ES; ++t) {
+                    const int i = lanes::entry(NS, G, sl.g, t);
+                    real acc = gterm(k, i);
+#pragma unroll
+                    for (int c = 0; c < NV; ++c) MADD(acc, BQP_HV(i * NV + c), v[c]);
+                    gs = fmax(gs, fabs(acc));
+                    if (k < N) {
+#pragma unroll
+                        for (int c = 0; c < NS; ++c) MADD(acc, Abar(c, i), pn[c]);
+                    }
+                    if (k > 0) acc -= W[L.qt_xpi + k * NS + i];
+                    W[L.rs + k * NS + i] = acc;
+                }
+#pragma unroll
+                for (int i = 0; i < NU; ++i) {
+                    real acc = gterm(k, NS + i);
+#pragma unroll
+                    for (int c = 0; c < NV; ++c) MADD(acc, BQP_HV((NS + i) * NV + c), v[c]);
+                    gu[i] = acc;
+                    gs = fmax(gs, fabs(acc));
+                }
+#pragma unroll
+                for (int i = 0; i < NU; ++i) {
+                    real acc = gu[i];
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) MADD(acc, Bbar(c, i), pn[c]);
+                    W[L.ru + k * NU + i] = (k < N) ? acc : 0.0;
+                }
+                if (k < N) {
+#pragma unroll
+                    for (int t = 0; t < ES; ++t) {
+                        const int i = lanes::entry(NS, G, sl.g, t);
+                        real acc = cb(i) - W[L.xs + (k + 1) * NS + i];
+#pragma unroll
+                        for (int c = 0; c < NS; ++c) MADD(acc, Abar(i, c), s[0][c]);
+#pragma unroll
+                        for (int c = 0; c < NU; ++c) MADD(acc, Bbar(i, c), u[0][c]);
+                        W[L.re + k * NS + i] = acc;
+                        fe = fmax(fe, fabs(acc));
+                    }
+                }
+            }
+            feasA = wmax(fe);
+            gsA = wmax(gs);
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k > N) continue;
             BQP_HK(k);
             real v[NV];
@@ -472,7 +558,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             for (int i = 0; i < NV; ++i) {
                 real acc = gterm(k, i);
 #pragma unroll
-                for (int c = 0; c < NV; ++c) acc += BQP_HV(i * NV + c) * v[c];
+                for (int c = 0; c < NV; ++c) MADD(acc, BQP_HV(i * NV + c), v[c]);
                 gv[i] = acc;
                 gs = fmax(gs, fabs(acc));
             }
@@ -484,7 +570,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 real acc = gv[i];
                 if (k < N) {
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) acc += Abar(c, i) * pn[c];
+                    for (int c = 0; c < NS; ++c) MADD(acc, Abar(c, i), pn[c]);
                 }
                 if (k > 0) acc -= pi[j][i];
                 W[L.rs + k * NS + i] = acc;
@@ -493,7 +579,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             for (int i = 0; i < NU; ++i) {
                 real acc = gv[NS + i];
 #pragma unroll
-                for (int c = 0; c < NS; ++c) acc += Bbar(c, i) * pn[c];
+                for (int c = 0; c < NS; ++c) MADD(acc, Bbar(c, i), pn[c]);
                 W[L.ru + k * NU + i] = (k < N) ? acc : 0.0;
             }
             if (k < N) {
@@ -501,9 +587,9 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int i = 0; i < NS; ++i) {
                     real acc = cb(i) - W[L.xs + (k + 1) * NS + i];
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) acc += Abar(i, c) * s[j][c];
+                    for (int c = 0; c < NS; ++c) MADD(acc, Abar(i, c), s[j][c]);
 #pragma unroll
-                    for (int c = 0; c < NU; ++c) acc += Bbar(i, c) * u[j][c];
+                    for (int c = 0; c < NU; ++c) MADD(acc, Bbar(i, c), u[j][c]);
                     if constexpr (!LNG) W[L.re + k * NS + i] = acc;
                     fe = fmax(fe, fabs(acc));
                 }
@@ -520,9 +606,9 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         if constexpr (PC) { if (rez) return real(0); }
         real acc = cb(i) - W[L.xs + (k + 1) * NS + i];
 #pragma unroll
-        for (int c = 0; c < NS; ++c) acc += Abar(i, c) * s[j][c];
+        for (int c = 0; c < NS; ++c) MADD(acc, Abar(i, c), s[j][c]);
 #pragma unroll
-        for (int c = 0; c < NU; ++c) acc += Bbar(i, c) * u[j][c];
+        for (int c = 0; c < NU; ++c) MADD(acc, Bbar(i, c), u[j][c]);
         return acc;
     };
 
@@ -530,13 +616,16 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     //      return the stationarity norm ----
     auto combine = [&]() __attribute__((always_inline)) -> real {
         const int lane = opq(lane_w);
+        // G > 1: the whole stage on every lane of it (the pass is five loads and ten box terms; by
+        // entries it was no shorter).  Every lane loads rs_k / ru_k before any
+        // lane stores them, and all store the same values
         real gpp[NV];
 #pragma unroll
         for (int c = 0; c < NV; ++c) gpp[c] = W[L.gpp + c];
         real st = 0;
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k > N) continue;
             real r[NS], ru[NU];
 #pragma unroll
@@ -830,9 +919,50 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     //   bw_k = Bbar' w_k (the post-backward pass adds it to Bbar' p_{k+1}).
     auto prep_iter = [&]() __attribute__((always_inline)) {
         const int lane = opq(lane_w);
+        if constexpr (G > 1) {
+            // lane (k, g): w_k and bw_k whole on every lane of the stage (w_k feeds every entry of
+            // cw_k: 25 of the pass's 80 multiply-adds at NS = 5), its ES entries of cw_k
+            const lanes::StageLane sl = lanes::stage_lane(lane, N, G);
+            const int k = sl.k;
+            if (k < N) {
+                const real* Pn = W + L.P + (k + 1) * PST;
+                const real* Kk = W + L.K + k * NU * NS;
+                real rek[NS], wk[NS];
+#pragma unroll
+                for (int c = 0; c < NS; ++c) rek[c] = W[L.re + k * NS + c];
+#pragma unroll
+                for (int i = 0; i < NS; ++i) {
+                    real v = 0.0;
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) MADD(v, Pn[pk_idx(NS, i, c)], rek[c]);
+                    wk[i] = v;
+                }
+#pragma unroll
+                for (int x = 0; x < NU; ++x) {
+                    real v = 0.0;
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(c, x), wk[c]);
+                    W[L.bw + k * NU + x] = v;
+                }
+#pragma unroll
+                for (int t = 0; t < ES; ++t) {
+                    const int i = lanes::entry(NS, G, sl.g, t);
+                    real v = 0.0;
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) {
+                        real ph = Abar(c, i);
+#pragma unroll
+                        for (int x = 0; x < NU; ++x) MADD(ph, Bbar(c, x), Kk[x * NS + i]);
+                        MADD(v, ph, wk[c]);
+                    }
+                    W[L.wv + k * NS + i] = v;
+                }
+            }
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k < N) {
                 real Pn_[LNG ? PST : 1];
                 const real* Pn = W + L.P + (k + 1) * PST;
@@ -845,14 +975,14 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int i = 0; i < NS; ++i) {
                     real v = 0.0;
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) v += Pn[pk_idx(NS, i, c)] * rek[c];
+                    for (int c = 0; c < NS; ++c) MADD(v, Pn[pk_idx(NS, i, c)], rek[c]);
                     wk[i] = v;
                 }
 #pragma unroll
                 for (int x = 0; x < NU; ++x) {
                     real v = 0.0;
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) v += Bbar(c, x) * wk[c];
+                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(c, x), wk[c]);
                     W[L.bw + k * NU + x] = v;
                 }
 #pragma unroll
@@ -862,8 +992,8 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                     for (int c = 0; c < NS; ++c) {
                         real ph = Abar(c, i);
 #pragma unroll
-                        for (int x = 0; x < NU; ++x) ph += Bbar(c, x) * Kk[x * NS + i];
-                        v += ph * wk[c];
+                        for (int x = 0; x < NU; ++x) MADD(ph, Bbar(c, x), Kk[x * NS + i]);
+                        MADD(v, ph, wk[c]);
                     }
                     W[L.wv + k * NS + i] = v;
                 }
@@ -877,13 +1007,62 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     const int li = lane < NS ? lane : NS - 1;
     auto solve = [&](int ods, int odu) __attribute__((always_inline)) {
         const int lane = opq(lane_w);
-        real qs[SPL][NS], qu[SPL][NU];
+        real qs[SPL][G > 1 ? ES : NS], qu[SPL][NU];
+        if constexpr (G > 1) {
+            const lanes::StageLane sl = lanes::stage_lane(lane, N, G);
+            // lane (k, g): its ES entries of qs and of the pre-pass (the cw_k entries it reads are
+            // the ones it wrote in prep_iter), qu on every lane of the stage
+            const int k = sl.k;
+            const int kk = k <= N ? k : N;
+            int ei[ES];
+#pragma unroll
+            for (int t = 0; t < ES; ++t) {
+                ei[t] = lanes::entry(NS, G, sl.g, t);
+                qs[0][t] = W[L.rs + kk * NS + ei[t]];
+                if (ei[t] < NX) {
+                    real e = 0.0;
+                    e += W[L.ebox + (kk * NB + ei[t]) * 2];
+                    e -= W[L.ebox + (kk * NB + ei[t]) * 2 + 1];
+                    qs[0][t] += e;
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < NU; ++i) {
+                real e = W[L.ru + kk * NU + i];
+                e += W[L.ebox + (kk * NB + NX + i) * 2];
+                e -= W[L.ebox + (kk * NB + NX + i) * 2 + 1];
+                qu[0][i] = e;
+            }
+            if (k == kp) {
+#pragma unroll
+                for (int t = 0; t < ES; ++t) qs[0][t] += W[L.gpe + ei[t]];
+                if (kp < N) {
+#pragma unroll
+                    for (int i = 0; i < NU; ++i) qu[0][i] += W[L.gpe + NS + i];
+                }
+            }
+            if (k < N) {
+                const real* Kk = W + L.K + k * NU * NS;
+#pragma unroll
+                for (int t = 0; t < ES; ++t) {
+                    real qq = qs[0][t];
+#pragma unroll
+                    for (int x = 0; x < NU; ++x) MADD(qq, Kk[x * NS + ei[t]], qu[0][x]);
+                    W[L.qt_xpi + k * NS + ei[t]] = qq + W[L.wv + k * NS + ei[t]];
+                }
+#pragma unroll
+                for (int x = 0; x < NU; ++x) W[L.qu + k * NU + x] = qu[0][x];
+            } else if (k == N) {
+#pragma unroll
+                for (int t = 0; t < ES; ++t) W[L.pv + N * NS + ei[t]] = qs[0][t];
+            }
+        } else {
         real gpe[NV];
 #pragma unroll
         for (int c = 0; c < NV; ++c) gpe[c] = W[L.gpe + c];
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             const int kk = k <= N ? k : N;
 #pragma unroll
             for (int i = 0; i < NS; ++i) qs[j][i] = W[L.rs + kk * NS + i];
@@ -924,14 +1103,14 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         // not depend on p_{k+1}, so the sequential sweep is one NS x NS mat-vec per stage.
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k < N) {
                 const real* Kk = W + L.K + k * NU * NS;
 #pragma unroll
                 for (int i = 0; i < NS; ++i) {
                     real qq = qs[j][i];
 #pragma unroll
-                    for (int x = 0; x < NU; ++x) qq += Kk[x * NS + i] * qu[j][x];
+                    for (int x = 0; x < NU; ++x) MADD(qq, Kk[x * NS + i], qu[j][x]);
                     W[L.qt_xpi + k * NS + i] = qq + W[L.wv + k * NS + i];
                 }
 #pragma unroll
@@ -940,6 +1119,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
 #pragma unroll
                 for (int i = 0; i < NS; ++i) W[L.pv + N * NS + i] = qs[j][i];
             }
+        }
         }
         wave_sync();
         STAMP(10);
@@ -994,9 +1174,37 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         wave_sync();
         STAMP(11);
         // post-backward: kff_k = -Rhat^{-1}((qu_k + bw_k) + Bbar' p_{k+1}); f_k = Bbar kff_k + re_k
+        if constexpr (G > 1) {
+            // lane (k, g): kff_k on every lane of the stage, its ES entries of f_k
+            const lanes::StageLane sl = lanes::stage_lane(lane, N, G);
+            const int k = sl.k;
+            if (k < N) {
+                real y[NS], r[NU];
+#pragma unroll
+                for (int i = 0; i < NS; ++i) y[i] = W[L.pv + (k + 1) * NS + i];
+#pragma unroll
+                for (int x = 0; x < NU; ++x) {
+                    real v = qu[0][x] + W[L.bw + k * NU + x];
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(c, x), y[c]);
+                    r[x] = -v;
+                }
+                chol_solve_small<NU>(W + L.Lr + k * NU * NU, r);
+#pragma unroll
+                for (int x = 0; x < NU; ++x) kff[0][x] = r[x];
+#pragma unroll
+                for (int t = 0; t < ES; ++t) {
+                    const int i = lanes::entry(NS, G, sl.g, t);
+                    real v = W[L.re + k * NS + i];
+#pragma unroll
+                    for (int x = 0; x < NU; ++x) MADD(v, Bbar(i, x), kff[0][x]);
+                    W[L.fv + k * NS + i] = v;
+                }
+            }
+        } else {
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k < N) {
                 real y[NS], r[NU];
 #pragma unroll
@@ -1005,7 +1213,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int x = 0; x < NU; ++x) {
                     real v = qu[j][x] + W[L.bw + k * NU + x];
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) v += Bbar(c, x) * y[c];
+                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(c, x), y[c]);
                     r[x] = -v;
                 }
                 chol_solve_small<NU>(W + L.Lr + k * NU * NU, r);
@@ -1015,10 +1223,11 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int i = 0; i < NS; ++i) {
                     real v = LNG ? re_at(j, k, i) : W[L.re + k * NS + i];
 #pragma unroll
-                    for (int x = 0; x < NU; ++x) v += Bbar(i, x) * kff[j][x];
+                    for (int x = 0; x < NU; ++x) MADD(v, Bbar(i, x), kff[j][x]);
                     W[L.fv + k * NS + i] = v;
                 }
             }
+        }
         }
         wave_sync();
         STAMP(12);
@@ -1077,14 +1286,14 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         // post-forward: du_k = K_k ds_k + kff_k
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k < N) {
                 const real* Kk = W + L.K + k * NU * NS;
 #pragma unroll
                 for (int x = 0; x < NU; ++x) {
                     real v = kff[j][x];
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) v += Kk[x * NS + c] * W[ods + k * NS + c];
+                    for (int c = 0; c < NS; ++c) MADD(v, Kk[x * NS + c], W[ods + k * NS + c]);
                     W[odu + k * NU + x] = v;
                 }
             } else if (k == N) {
@@ -1104,7 +1313,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         const int lane = opq(lane_w);
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k > N || k < 1) continue;
             real dsk[NS];
 #pragma unroll
@@ -1116,7 +1325,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             for (int i = 0; i < NS; ++i) {
                 real v = W[L.pv + k * NS + i];
 #pragma unroll
-                for (int c = 0; c < NS; ++c) v += Pk[pk_idx(NS, i, c)] * dsk[c];
+                for (int c = 0; c < NS; ++c) MADD(v, Pk[pk_idx(NS, i, c)], dsk[c]);
                 W[L.wv + k * NS + i] = v;
             }
         }
@@ -1125,17 +1334,17 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         const int lane = opq(lane_w);
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k > N) continue;
             if (k >= 1) {
 #pragma unroll
-                for (int i = 0; i < NS; ++i) pi[j][i] += al * W[L.wv + k * NS + i];
+                for (int i = 0; i < NS; ++i) MADD(pi[j][i], al, W[L.wv + k * NS + i]);
             }
 #pragma unroll
-            for (int i = 0; i < NS; ++i) s[j][i] += al * W[ids + k * NS + i];
+            for (int i = 0; i < NS; ++i) MADD(s[j][i], al, W[ids + k * NS + i]);
             if (k < N) {
 #pragma unroll
-                for (int i = 0; i < NU; ++i) u[j][i] += al * W[idu + k * NU + i];
+                for (int i = 0; i < NU; ++i) MADD(u[j][i], al, W[idu + k * NU + i]);
             }
         }
     };
@@ -1143,7 +1352,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         const int lane = opq(lane_w);
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k > N) continue;
             real dsk[NS];
 #pragma unroll
@@ -1156,15 +1365,15 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int i = 0; i < NS; ++i) {
                     real v = W[L.pv + k * NS + i];
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) v += Pk[pk_idx(NS, i, c)] * dsk[c];
-                    pi[j][i] += al * v;
+                    for (int c = 0; c < NS; ++c) MADD(v, Pk[pk_idx(NS, i, c)], dsk[c]);
+                    MADD(pi[j][i], al, v);
                 }
             }
 #pragma unroll
-            for (int i = 0; i < NS; ++i) s[j][i] += al * dsk[i];
+            for (int i = 0; i < NS; ++i) MADD(s[j][i], al, dsk[i]);
             if (k < N) {
 #pragma unroll
-                for (int i = 0; i < NU; ++i) u[j][i] += al * W[idu + k * NU + i];
+                for (int i = 0; i < NU; ++i) MADD(u[j][i], al, W[idu + k * NU + i]);
             }
         }
     };
@@ -1179,7 +1388,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         constexpr int SW = hand_stage_w(NS, NU);
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k > N) continue;
 #pragma unroll
             for (int i = 0; i < NS; ++i) {
@@ -1303,7 +1512,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             // to its output now (overwritten below only if the polish is accepted)
 #pragma unroll
             for (int j = 0; j < SPL; ++j) {
-                const int k = lane + WAVE * j;
+                const int k = lane + WAVE * j;            // one lane per stage (G > 1: group 0)
                 if (a.pi_out && k >= 1 && k <= N) {
                     double* po = a.pi_out + ((int64_t)inst * N + (k - 1)) * NX;
 #pragma unroll
@@ -1322,7 +1531,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             auto zero_stage_res = [&]() __attribute__((always_inline)) {
 #pragma unroll
                 for (int j = 0; j < SPL; ++j) {
-                    const int k = lane + WAVE * j;
+                    const int k = stage_of(lane, j);
                     if (k > N) continue;
 #pragma unroll
                     for (int i = 0; i < NS; ++i) {
@@ -1408,7 +1617,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 pi_kept = true;
 #pragma unroll
                 for (int j = 0; j < SPL; ++j) {
-                    const int k = lane + WAVE * j;
+                    const int k = stage_of(lane, j);
                     if (k <= N) {
 #pragma unroll
                         for (int i = 0; i < NS; ++i) s[j][i] = W[L.dsv + k * NS + i];
@@ -1427,7 +1636,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         constexpr int SW = hand_stage_w(NS, NU);
 #pragma unroll
         for (int j = 0; j < SPL; ++j) {
-            const int k = lane + WAVE * j;
+            const int k = stage_of(lane, j);
             if (k > N) continue;
 #pragma unroll
             for (int i = 0; i < NS; ++i) { hb[k * SW + i] = (float)s[j][i]; hb[k * SW + NS + i] = (float)pi[j][i]; }
@@ -1441,6 +1650,8 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         }
         return;
     }
+    // one lane per stage (G > 1: group 0, lanes 0..N), so the wave sum of fval keeps its terms in
+    // the lanes it had them in
     real fv = 0.0;
 #pragma unroll
     for (int j = 0; j < SPL; ++j) {
@@ -1492,6 +1703,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
 
 #undef BQP_HK
 #undef BQP_HV
+#undef MADD
 
 // ==========================================================================================
 // row wave
@@ -2632,7 +2844,7 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
 // ==========================================================================================
 // kernel: QPB instances per workgroup, waves [0, QPB) stage waves, [QPB, 2 QPB) row waves
 // ==========================================================================================
-template <int NX, int NU, int NP, int SPL, int RPL, int BPL, bool POL, bool QUEUE>
+template <int NX, int NU, int NP, int SPL, int RPL, int BPL, bool POL, bool QUEUE, int G>
 __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
     constexpr int NS = NX + NP;
     constexpr int NV = NS + NU;
@@ -2716,11 +2928,11 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
         if (rowwave && lane == 0)
             *reinterpret_cast<int*>(W + L.xch + X_NEXT + xnext) = atomicAdd(a.queue, 1) + (int)gridDim.x * qpb;
 #if defined(BQP_EXP_ONLY)   // register-budget diagnostic: one wave's code alone (never run)
-        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
+        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL, G>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
         else row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fsi, lds, lane, inst);
 #else
         if (!rowwave)
-            stage_wave<NX, NU, NP, SPL, POL>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
+            stage_wave<NX, NU, NP, SPL, POL, G>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
         else
             row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fsi, lds, lane, inst);
 #endif
@@ -2755,11 +2967,11 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
             wave_sync();
         }
 #if defined(BQP_EXP_ONLY)   // register-budget diagnostic: one wave's code alone (never run)
-        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL>(a, W, L, Hs, lane, inst, inst);
+        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL, G>(a, W, L, Hs, lane, inst, inst);
         else row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fs, lds, lane, inst);
 #else
         if (!rowwave)
-            stage_wave<NX, NU, NP, SPL, POL>(a, W, L, Hs, lane, inst, inst);
+            stage_wave<NX, NU, NP, SPL, POL, G>(a, W, L, Hs, lane, inst, inst);
         else
             row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fs, lds, lane, inst);
 #endif
@@ -2800,24 +3012,24 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
 // the solve kernel (no polish code: the main loop keeps its register budget), the repair kernel
 // (same IPM, then the active-set polish) over the instances the solve kernel marked, and the
 // persistent solve kernel (work queue) for batches beyond the resident workgroups
-template <int NX, int NU, int NP, int SPL, int RPL, int BPL>
+template <int NX, int NU, int NP, int SPL, int RPL, int BPL, int G>
 __global__ void __launch_bounds__(SPL == 2 ? 256 : 512) ocp_ipm_kernel(OcpKernelArgs a) {
-    ocp_body<NX, NU, NP, SPL, RPL, BPL, false, false>(a);
+    ocp_body<NX, NU, NP, SPL, RPL, BPL, false, false, G>(a);
 }
-template <int NX, int NU, int NP, int SPL, int RPL, int BPL>
+template <int NX, int NU, int NP, int SPL, int RPL, int BPL, int G>
 __global__ void __launch_bounds__(SPL == 2 ? 256 : 512) ocp_polish_kernel(OcpKernelArgs a) {
-    ocp_body<NX, NU, NP, SPL, RPL, BPL, true, false>(a);
+    ocp_body<NX, NU, NP, SPL, RPL, BPL, true, false, G>(a);
 }
 #ifndef BQP_DI_OCC3
 #define BQP_DI_OCC3 0
 #endif
 // A/B variant (make ab VFLAGS=-DBQP_DI_OCC3=1; host: BQP_OCP_WPB=5): the DI queue kernel with five
 // instances per workgroup (145 KB of LDS) and three waves per SIMD (168 VGPRs) - VERDICT r5 item 4
-template <int NX, int NU, int NP, int SPL, int RPL, int BPL>
+template <int NX, int NU, int NP, int SPL, int RPL, int BPL, int G>
 __global__ void __launch_bounds__(SPL == 2 ? 256 : ((BQP_DI_OCC3 && NX == 2) ? 640 : 512),
                                   (BQP_DI_OCC3 && NX == 2 && SPL == 1) ? 3 : 1)
 ocp_queue_kernel(OcpKernelArgs a) {
-    ocp_body<NX, NU, NP, SPL, RPL, BPL, false, true>(a);
+    ocp_body<NX, NU, NP, SPL, RPL, BPL, false, true, G>(a);
 }
 
 }  // namespace dp / sp
@@ -2851,15 +3063,15 @@ static hipError_t lds_attr(const void* k, size_t lds) {
     return e;
 }
 
-template <int NX, int NU, int NP, int SPL, int RPL, int BPL>
+template <int NX, int NU, int NP, int SPL, int RPL, int BPL, int G = 1>
 static hipError_t launch_t(const OcpKernelArgs& a0, int blocks, size_t lds, hipStream_t st, bool pol) {
 #ifdef BQP_F32
     (void)pol;
-    auto k = sp::ocp_ipm_kernel<NX, NU, NP, SPL, RPL, BPL>;
-    auto kq = sp::ocp_queue_kernel<NX, NU, NP, SPL, RPL, BPL>;
+    auto k = sp::ocp_ipm_kernel<NX, NU, NP, SPL, RPL, BPL, G>;
+    auto kq = sp::ocp_queue_kernel<NX, NU, NP, SPL, RPL, BPL, G>;
 #else
-    auto k = pol ? dp::ocp_polish_kernel<NX, NU, NP, SPL, RPL, BPL> : dp::ocp_ipm_kernel<NX, NU, NP, SPL, RPL, BPL>;
-    auto kq = dp::ocp_queue_kernel<NX, NU, NP, SPL, RPL, BPL>;
+    auto k = pol ? dp::ocp_polish_kernel<NX, NU, NP, SPL, RPL, BPL, G> : dp::ocp_ipm_kernel<NX, NU, NP, SPL, RPL, BPL, G>;
+    auto kq = dp::ocp_queue_kernel<NX, NU, NP, SPL, RPL, BPL, G>;
 #endif
     OcpKernelArgs a = a0;
     // persistent launch (ocp_queue_kernel) when the batch needs more workgroups than fit on the
@@ -2889,15 +3101,36 @@ static hipError_t launch_t(const OcpKernelArgs& a0, int blocks, size_t lds, hipS
 // box rows per lane (BPL): all (N+1) 2 (nx+nu) box rows spread over the 64 lanes; the stage
 // layout per lane (SPL) is tied to it: SPL 1 (N < 64) -> 4 (<= 256 rows) or 10 (<= 640),
 // SPL 2 -> 16 (<= 1024) or 20 (<= 1280)
-template <int NX, int NU, int NP, int SPL, int BPL>
-static hipError_t launch_rpl(const OcpKernelArgs& a, int rpl, int blocks, size_t lds, hipStream_t st, bool pol) {
+template <int NX, int NU, int NP, int SPL, int BPL, int G>
+static hipError_t launch_rpl_g(const OcpKernelArgs& a, int rpl, int blocks, size_t lds, hipStream_t st, bool pol) {
     switch (rpl) {
-        case 1: return launch_t<NX, NU, NP, SPL, 1, BPL>(a, blocks, lds, st, pol);
-        case 4: return launch_t<NX, NU, NP, SPL, 4, BPL>(a, blocks, lds, st, pol);
-        case 10: return launch_t<NX, NU, NP, SPL, 10, BPL>(a, blocks, lds, st, pol);
-        case 16: return launch_t<NX, NU, NP, SPL, 16, BPL>(a, blocks, lds, st, pol);
+        case 1: return launch_t<NX, NU, NP, SPL, 1, BPL, G>(a, blocks, lds, st, pol);
+        case 4: return launch_t<NX, NU, NP, SPL, 4, BPL, G>(a, blocks, lds, st, pol);
+        case 10: return launch_t<NX, NU, NP, SPL, 10, BPL, G>(a, blocks, lds, st, pol);
+        case 16: return launch_t<NX, NU, NP, SPL, 16, BPL, G>(a, blocks, lds, st, pol);
         default: return hipErrorInvalidValue;
     }
+}
+
+// BQP_OCP_LANE_GROUPS = 1, 2 or 3: at most that many lane groups in the stage wave (clamped to
+// what the horizon allows and the family has compiled); 1 runs the one-lane-per-stage kernels
+[[maybe_unused]] static inline int lane_groups_cap() {
+    const char* e = getenv("BQP_OCP_LANE_GROUPS");
+    const int v = e ? atoi(e) : lanes::MAX_GROUPS;
+    return v >= 1 && v <= lanes::MAX_GROUPS ? v : lanes::MAX_GROUPS;
+}
+
+// lane groups of the stage wave (bqp_lanes.h groups_for): the family's G > 1 instantiation exists
+// for SPL 1 / BPL 4 only (MG: G = 3, N <= 20), every other shape runs G = 1
+template <int NX, int NU, int NP, int SPL, int BPL>
+static hipError_t launch_rpl(const OcpKernelArgs& a, int rpl, int blocks, size_t lds, hipStream_t st, bool pol) {
+    constexpr int NS = NX + NP;
+    constexpr int GM = (SPL == 1 && BPL == 4 && lanes::compiled(NS, NU, 3)) ? 3 : 1;
+    if constexpr (GM > 1) {
+        if (lanes::groups_for(a.N, NS, NU, BPL, lane_groups_cap()) == GM)
+            return launch_rpl_g<NX, NU, NP, SPL, BPL, GM>(a, rpl, blocks, lds, st, pol);
+    }
+    return launch_rpl_g<NX, NU, NP, SPL, BPL, 1>(a, rpl, blocks, lds, st, pol);
 }
 
 template <int NX, int NU, int NP>
@@ -2917,6 +3150,7 @@ hipError_t BQP_CAT(launch_ocp_di, BQP_SFX)(const OcpKernelArgs& a, int spl, int 
 hipError_t BQP_CAT(launch_ocp_mg, BQP_SFX)(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st, bool pol) {
 #if defined(BQP_ISA_ONLY_MG10)
     // codegen inspection build (make isa): the MG N<64, 616-row instance only
+    if (spl == 1 && rpl == 10 && 3 * (a.N + 1) <= WAVE) return launch_t<4, 1, 1, 1, 10, 4, 3>(a, blocks, lds, st, pol);
     if (spl == 1 && rpl == 10 && a.N + 1 <= 25) return launch_t<4, 1, 1, 1, 10, 4>(a, blocks, lds, st, pol);
     return hipErrorInvalidValue;
 #elif defined(BQP_ISA_ONLY_MG_LNG)
