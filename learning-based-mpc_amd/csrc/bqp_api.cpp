@@ -386,10 +386,20 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
         HIP_TRY(h->pwork.reserve(sizeof(double) * (size_t)batch * (N + 1) * bqp::ocp_pstride(nx + np)));
         Pg = h->pwork.p;
     }
-    HIP_TRY(bqp::launch_ocp_prep(D->W, mp > 0 ? D->Fp : D->W, nx, nu, np, N, mp, d->poly_stage,
-                                 hstride, mpad, Hd, Fd, queues, st));
+    // Shared tables at short horizons: the solve and repair kernels form the prepared layout
+    // themselves while they stage the caller's W and Fp into LDS, so the call has no prep launch
+    // (and no dependent dispatch in front of the solve).  Long horizons read H from global, and
+    // per-instance W / Fp have their own paths: those keep the prepared tables.
+    // BQP_OCP_PREP_LAUNCH=1 forces the prep launch everywhere (A/B timing, the bitwise test).
+    const char* prep_env = getenv("BQP_OCP_PREP_LAUNCH");
+    const bool raw_tables = N + 1 <= 64 && !hinst && !fpi && !(prep_env && atoi(prep_env) == 1);
+    if (!raw_tables)
+        HIP_TRY(bqp::launch_ocp_prep(D->W, mp > 0 ? D->Fp : D->W, nx, nu, np, N, mp, d->poly_stage,
+                                     hstride, mpad, Hd, Fd, queues, st));
     bqp::OcpKernelArgs a;
     memset(&a, 0, sizeof(a));
+    a.raw_tables = raw_tables ? 1 : 0;
+    a.queue_zeroed = raw_tables ? 0 : 1;
     // the solve launch's work queue (used when the batch exceeds the resident workgroups)
     a.queue = queues;
     a.N = N; a.mp = mp; a.kp = d->poly_stage; a.batch = batch; a.wpb = wpb;
@@ -400,7 +410,8 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
     a.tol_comp = o.tol_comp; a.tau = o.tau;
     a.polish = o.polish < 0 ? 0 : (o.polish == 0 ? 1 : std::min(o.polish, 2));
     a.pol_need = polneed;
-    a.H = Hd; a.Fp = Fd;
+    a.H = raw_tables ? D->W : Hd;
+    a.Fp = raw_tables ? (mp > 0 ? D->Fp : D->W) : Fd;
     a.A = D->A; a.B = D->B; a.c = D->c; a.w = D->w; a.xlb = D->xlb; a.xub = D->xub;
     a.ulb = D->ulb; a.uub = D->uub; a.hp = mp > 0 ? D->hp : Hd; a.x0 = D->x0;
     a.sA = D->sA; a.sB = D->sB; a.sc = D->sc; a.sw = D->sw; a.sxb = D->sxb; a.sub = D->sub;

@@ -20,9 +20,16 @@ struct OcpKernelArgs {
     int N, mp, kp, batch, wpb, hstride, mpad, shared_doubles, max_iter;
     // persistent work queue: when the batch needs more workgroups than the
     // device holds at once, the launch is sized to the resident workgroups and every instance
-    // slot (stage / row wave pair) takes its next instance from this counter (zeroed by the prep
-    // kernel) as soon as its current one is done; nullptr: one instance per slot, grid = batch
+    // slot (stage / row wave pair) takes its next instance from this counter as soon as its
+    // current one is done; nullptr: one instance per slot, grid = batch.  The counter is zeroed by
+    // the prep kernel where that runs (queue_zeroed = 1), else by the launch helper right before a
+    // persistent launch (launch_ocp_queue_zero) - a launch of one instance per slot never reads it
     int* queue;
+    int queue_zeroed;
+    // 1: H and Fp are the caller's arrays (bqp_ocp_data W and Fp, external order) and the kernel
+    // forms the prepared layout below while it stages them into LDS, so no prep launch is needed
+    // (shared tables, N + 1 <= 64); 0: H and Fp are the tables ocp_prep_kernel wrote
+    int raw_tables;
     double tol_stat, tol_feas, tol_comp, tau;
     const double* H;
     const double* Fp;
@@ -82,6 +89,7 @@ hipError_t launch_ocp_f32(const OcpKernelArgs& a, int nx, int nu, int np, hipStr
 hipError_t launch_ocp_prep(const double* W, const double* Fp, int nx, int nu, int np, int N,
                            int mp, int kp, int hstride, int mpad, double* Hout, double* Fout,
                            int* qzero, hipStream_t st);
+hipError_t launch_ocp_queue_zero(int* q, hipStream_t st);   // one work-queue counter to 0
 hipError_t launch_ocp_prep_h(const double* W, int64_t sW, int batch, int nx, int nu, int np,
                              int N, int hstride, double* Hout, hipStream_t st);
 hipError_t launch_ocp_finalize(const double* stats, int batch, void* out, hipStream_t st);

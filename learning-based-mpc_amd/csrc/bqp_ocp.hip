@@ -797,10 +797,10 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             for (int v = 0; v < VAL; ++v) {
                 const int s = v & 3;
                 const real src = mv[v >> 2];
-                g[v] = (s == 0) ? dpp_mov<0x00, 0xf>(real(0), src)
-                     : (s == 1) ? dpp_mov<0x55, 0xf>(real(0), src)
-                     : (s == 2) ? dpp_mov<0xAA, 0xf>(real(0), src)
-                                : dpp_mov<0xFF, 0xf>(real(0), src);
+                g[v] = (s == 0) ? dpp_mov0<0x00>(src)
+                     : (s == 1) ? dpp_mov0<0x55>(src)
+                     : (s == 2) ? dpp_mov0<0xAA>(src)
+                                : dpp_mov0<0xFF>(src);
             }
             real pv, Kc[NU], Lf[NU * NU];
             if constexpr (NU == 1) {
@@ -1148,9 +1148,17 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
 #pragma unroll
                 for (int x = 0; x < NU; ++x) kc[x] = W[L.K + k * NU * NS + x * NS + li];
             };
+            // The refills are unconditional (the stage index clamped at 0: past the last stage a
+            // set is refilled with stage 0 again and not used) and the loop takes whole stage
+            // pairs with its only exit at the bottom, the single stage of an odd N after it.  A
+            // guarded refill or an exit between the two steps of a trip gives the loop header a
+            // path on which the operands of the next step are the newest loads, and the
+            // compiler's wait at the header must cover every path: it drained the LDS queue
+            // (lgkmcnt(0)) once per trip, exposing one load latency per two stages.  So every
+            // path has the same loads in flight and the header wait leaves the newest refill out.
             real k0[NU], q0, k1[NU], q1;
             load_b(N - 1, k0, q0);
-            if (N >= 2) load_b(N - 2, k1, q1);
+            load_b(max(N - 2, 0), k1, q1);
             auto step_b = [&](int k, const real (&kc)[NU], real q) __attribute__((always_inline)) {
                 real acc = q;
 #pragma unroll
@@ -1163,13 +1171,13 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 if (lane < NS) W[L.pv + k * NS + lane] = acc;
                 rbc_all<0, NS>(acc, p);   // lanes c < NS of the row hold entry c
             };
-            for (int k = N - 1; k >= 0; k -= 2) {
+            for (int k = N - 1; k >= 1; k -= 2) {
                 step_b(k, k0, q0);
-                if (k >= 2) load_b(k - 2, k0, q0);
-                if (k == 0) break;
+                load_b(max(k - 2, 0), k0, q0);
                 step_b(k - 1, k1, q1);
-                if (k >= 3) load_b(k - 3, k1, q1);
+                load_b(max(k - 3, 0), k1, q1);
             }
+            if (N & 1) step_b(0, k0, q0);   // set 0 holds stage 0 (N = 1: from the first load)
         }
         wave_sync();
         STAMP(11);
@@ -1259,8 +1267,10 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                     for (int c = 0; c < NS; ++c) kr[x][c] = W[L.K + k * NU * NS + x * NS + c];
             };
             real k0[NU][NS], f0, k1[NU][NS], f1;
+            // unconditional refills (stage index clamped at N - 1) and whole stage pairs, as in
+            // the backward sweep
             load_f(0, k0, f0);
-            if (N >= 2) load_f(1, k1, f1);
+            load_f(min(1, N - 1), k1, f1);
             auto step_f = [&](int k, const real (&kr)[NU][NS], real f) __attribute__((always_inline)) {
                 real acc = f;
 #pragma unroll
@@ -1273,13 +1283,13 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 if (lane < NS) W[ods + (k + 1) * NS + lane] = acc;
                 rbc_all<0, NS>(acc, d);   // lanes c < NS of the row hold entry c
             };
-            for (int k = 0; k < N; k += 2) {
+            for (int k = 0; k + 1 < N; k += 2) {
                 step_f(k, k0, f0);
-                if (k + 2 < N) load_f(k + 2, k0, f0);
-                if (k + 1 >= N) break;
+                load_f(min(k + 2, N - 1), k0, f0);
                 step_f(k + 1, k1, f1);
-                if (k + 3 < N) load_f(k + 3, k1, f1);
+                load_f(min(k + 3, N - 1), k1, f1);
             }
+            if (N & 1) step_f(N - 1, k0, f0);   // set 0 holds stage N - 1
         }
         wave_sync();
         STAMP(13);
@@ -2273,7 +2283,7 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
                 if (bpres(b)) W[L.ebox + brow(b)] += smu * frcp(tx[b]);
         }
         // tot (from the joint reduction): lane 2c = Fp'e0 (c), lane 2c+1 = Fp'(1/t) (c)
-        const real other = dpp_mov<0xB1, 0xf>(real(0), tot);
+        const real other = dpp_mov0<0xB1>(tot);
         if (lane < 2 * NV && (lane & 1) == 0) W[L.gpe + lane / 2] = tot + smu * other;
     };
     // pure centring step (socf = 0): the predictor pass formed the corrector terms with
@@ -2878,10 +2888,40 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
     // the polytope rhs and box bounds when the batch shares them
     real* Hs = lds;
     real* Fs = lds + a.sh_F;
+    if (!LNG && a.raw_tables) {
+        // a.H / a.Fp are the caller's arrays (bqp_ocp_data W, Fp: external [x; u; theta] order,
+        // column-major); the prepared layout is formed while staging, with ocp_prep_kernel's map
+        // value for value (its launch is then not needed): internal [x; theta; u] row-major stages
+        // of HST elements with the pad element zero, the u rows and columns of stage N zero; Fp
+        // columns of MPAD rows, rows past mp zero, the u columns zero for a terminal set.  The
+        // host sets raw_tables only where both tables are shared and staged here (not LNG).
+        constexpr int HST = NV * NV + 1, MPAD = 64 * RPL;
+        auto ext = [](int i) { return i < NX ? i : (i < NS ? NX + NU + (i - NX) : NX + (i - NS)); };
+        for (int t = threadIdx.x; t < (N + 1) * HST; t += blockDim.x) {
+            const int k = t / HST, e = t - k * HST;
+            double v = 0.0;
+            if (e < NV * NV) {
+                const int i = e / NV, j = e - i * NV;
+                v = a.H[k * (NV * NV) + ext(j) * NV + ext(i)];
+                if (k == N && (i >= NS || j >= NS)) v = 0.0;
+            }
+            Hs[t] = v;
+        }
+        for (int q = threadIdx.x; q < NV * MPAD; q += blockDim.x) {
+            const int c = q / MPAD, r = q - c * MPAD;
+            double v = 0.0;
+            if (r < a.mp) {
+                v = a.Fp[ext(c) * a.mp + r];
+                if (a.kp == N && c >= NS) v = 0.0;
+            }
+            Fs[q] = v;
+        }
+    } else {
     if (!LNG && !a.H_inst)
         for (int i = threadIdx.x; i < (N + 1) * a.hstride; i += blockDim.x) Hs[i] = a.H[i];
     if (!fpi)
         for (int i = threadIdx.x; i < NV * a.mpad; i += blockDim.x) Fs[i] = a.Fp[i];
+    }
     if (a.sh_hp >= 0)
         for (int r = threadIdx.x; r < a.mp; r += blockDim.x) lds[a.sh_hp + r] = a.hp[r];
     if (LNG && a.sh_bnd >= 0) {
@@ -3088,6 +3128,10 @@ static hipError_t launch_t(const OcpKernelArgs& a0, int blocks, size_t lds, hipS
         if (e != hipSuccess) return e;
         const int resident = cus * (per_cu > 0 ? per_cu : 1);
         if (blocks > resident) {
+            // the counter is zeroed here, on the one path that reads it (a call that launched
+            // ocp_prep_kernel has zeroed it already: queue_zeroed)
+            if (!a.queue_zeroed)
+                if (hipError_t ez = launch_ocp_queue_zero(a.queue, st)) return ez;
             hipLaunchKernelGGL(kq, dim3(resident), dim3(128 * a.wpb), lds, st, a);
             return hipGetLastError();
         }

@@ -62,6 +62,15 @@ hipError_t launch_ocp_prep(const double* W, const double* Fp, int nx, int nu, in
     return hipGetLastError();
 }
 
+// what is left of the prep launch where the solve kernel stages the caller's tables itself
+// (OcpKernelArgs::raw_tables): the counter of a persistent launch, zeroed right before it
+__global__ void ocp_queue_zero_kernel(int* __restrict__ q) { *q = 0; }
+
+hipError_t launch_ocp_queue_zero(int* q, hipStream_t st) {
+    hipLaunchKernelGGL(ocp_queue_zero_kernel, dim3(1), dim3(1), 0, st, q);
+    return hipGetLastError();
+}
+
 // per-instance stage-cost tables (bqp_ocp_data.sW != 0): batch x (N+1) x hstride, same layout
 // as the shared table of ocp_prep_kernel
 __global__ void ocp_prep_h_kernel(const double* __restrict__ W, int64_t sW, int batch, int nx,

@@ -15,6 +15,17 @@ __device__ __forceinline__ void wave_sync() {
 // Wave-wide reductions on DPP lane moves (quad_perm xor1/xor2, row_half_mirror, row_mirror
 // inside each 16-lane row, then row_bcast15/31 across rows) + a readlane of lane 63: no LDS
 // traffic, result uniform in every lane.  EXEC must be full (all call sites are wave-uniform).
+//
+// Two forms of the lane move.  dpp_mov<CTRL, ROWM>(old, v) keeps `old` where the move delivers
+// nothing (rows outside ROWM, source lanes that are out of range or disabled), so the compiler
+// first writes `old` into the destination: one more VALU instruction per move.  dpp_mov0<CTRL>(v)
+// is the move with old = 0 and the full row mask, issued with bound_ctrl:1: a source lane that
+// is out of range or disabled then reads as 0, which is what the untouched old = 0 gave, and a
+// valid one delivers its value either way - the same function for every EXEC and every bit
+// pattern (the move copies bits; tests/hip/dpp_bcast_check.hip compares the two), without the
+// zero write.  Only that case may use it: a partial row mask (the row_bcast:15 / :31 steps)
+// leaves the masked rows at `old`, which bound_ctrl does not provide, and a non-zero `old`
+// (wmax's -inf) would only be equivalent while EXEC is full, so both stay on dpp_mov.
 template <int CTRL, int ROWM>
 __device__ __forceinline__ double dpp_mov(double old, double v) {
     const int2 o = __builtin_bit_cast(int2, old);
@@ -22,6 +33,14 @@ __device__ __forceinline__ double dpp_mov(double old, double v) {
     int2 r;
     r.x = __builtin_amdgcn_update_dpp(o.x, x.x, CTRL, ROWM, 0xf, false);
     r.y = __builtin_amdgcn_update_dpp(o.y, x.y, CTRL, ROWM, 0xf, false);
+    return __builtin_bit_cast(double, r);
+}
+template <int CTRL>
+__device__ __forceinline__ double dpp_mov0(double v) {
+    const int2 x = __builtin_bit_cast(int2, v);
+    int2 r;
+    r.x = __builtin_amdgcn_update_dpp(0, x.x, CTRL, 0xf, 0xf, true);
+    r.y = __builtin_amdgcn_update_dpp(0, x.y, CTRL, 0xf, 0xf, true);
     return __builtin_bit_cast(double, r);
 }
 __device__ __forceinline__ double lane63(double v) {
@@ -32,10 +51,10 @@ __device__ __forceinline__ double lane63(double v) {
     return __builtin_bit_cast(double, r);
 }
 __device__ __forceinline__ double wsum(double v) {
-    v += dpp_mov<0xB1, 0xf>(0.0, v);
-    v += dpp_mov<0x4E, 0xf>(0.0, v);
-    v += dpp_mov<0x141, 0xf>(0.0, v);
-    v += dpp_mov<0x140, 0xf>(0.0, v);
+    v += dpp_mov0<0xB1>(v);
+    v += dpp_mov0<0x4E>(v);
+    v += dpp_mov0<0x141>(v);
+    v += dpp_mov0<0x140>(v);
     v += dpp_mov<0x142, 0xa>(0.0, v);
     v += dpp_mov<0x143, 0xc>(0.0, v);
     return lane63(v);
@@ -99,14 +118,19 @@ __device__ __forceinline__ float dpp_mov(float old, float v) {
                                                                   __builtin_bit_cast(int, v), CTRL,
                                                                   ROWM, 0xf, false));
 }
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov0(float v) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL,
+                                                                  0xf, 0xf, true));
+}
 __device__ __forceinline__ float lane63(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
 __device__ __forceinline__ float wsum(float v) {
-    v += dpp_mov<0xB1, 0xf>(0.0f, v);
-    v += dpp_mov<0x4E, 0xf>(0.0f, v);
-    v += dpp_mov<0x141, 0xf>(0.0f, v);
-    v += dpp_mov<0x140, 0xf>(0.0f, v);
+    v += dpp_mov0<0xB1>(v);
+    v += dpp_mov0<0x4E>(v);
+    v += dpp_mov0<0x141>(v);
+    v += dpp_mov0<0x140>(v);
     v += dpp_mov<0x142, 0xa>(0.0f, v);
     v += dpp_mov<0x143, 0xc>(0.0f, v);
     return lane63(v);
@@ -127,15 +151,16 @@ __device__ __forceinline__ float rl(float v, int src) {
 
 // lane C's value in every lane of its 16-lane row (gfx950 DPP row_newbcast: one v_mov_b64_dpp
 // / v_mov_b32_dpp, the value stays in vector registers); rbc_all fills p[c] = lane c's v for
-// c < NC (NC <= 16), the sweep broadcast without a scalar round trip
+// c < NC (NC <= 16), the sweep broadcast without a scalar round trip.  old = 0 with bound_ctrl:1,
+// as dpp_mov0: no zero write in front of the move
 template <int C>
 __device__ __forceinline__ double rbc(double v) {
-    return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + C, 0xf, 0xf, false);
+    return __builtin_amdgcn_update_dpp(0.0, v, 0x150 + C, 0xf, 0xf, true);
 }
 template <int C>
 __device__ __forceinline__ float rbc(float v) {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v),
-                                                                 0x150 + C, 0xf, 0xf, false));
+                                                                 0x150 + C, 0xf, 0xf, true));
 }
 // the value of 16-lane row Q (lane 16 Q + l%16) in lane l of every row: v_permlane16_swap of a
 // register with itself gives the even / odd row pairs, v_permlane32_swap the halves - VALU only
@@ -163,7 +188,7 @@ __device__ __forceinline__ void tsum_step(const T (&in)[KI], T (&out)[KO], bool 
         const T b = (2 * p + 1 < KI) ? in[2 * p + 1] : T(0);
         const T keep = hi ? b : a;
         const T send = hi ? a : b;
-        out[p] = keep + dpp_mov<CTRL, 0xf>(T(0), send);
+        out[p] = keep + dpp_mov0<CTRL>(send);
     }
 }
 template <typename T, int K>
