@@ -286,7 +286,8 @@ int bqp_lbmpc_solve_batched_device(bqp_handle h, const bqp_lbmpc_dims* d, int ba
 #define BQP_PLANT_MG_RK4 1
 #define BQP_PLANT_MG_ODE23 2
 typedef struct {
-    int plant;           /* BQP_PLANT_MG_RK4 or BQP_PLANT_MG_ODE23 */
+    int plant;           /* BQP_PLANT_MG_RK4 or BQP_PLANT_MG_ODE23 (bqp_closed_loop_track: also
+                            BQP_PLANT_LINEAR) */
     int steps;           /* closed-loop steps (mpciterations) */
     double delta;        /* plant step (s) */
     const double* x_eq;  /* nx working point (device memory in the _device variant) */
@@ -375,6 +376,44 @@ int bqp_closed_loop_sqp_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
                                const bqp_options* opt, const bqp_closed_loop* cl,
                                const bqp_learning* lw, const double* x_init, double* X, double* U,
                                int* exitflag, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Closed loop with a reference schedule and a linear plant: the loop of
+ *   matlab/trackingMPC/RunExample.m:131-147  ("MPC for tracking piecewise constant references":
+ *       xs = set_ref(k), the F5 solve, x = getTransitions(x, u_0), art_refHistory)
+ * and of RunExample_robust.m (the same with an additive disturbance), for a whole batch; the
+ * schedule also moves the set-point of the Moore-Greitzer tracking loops above.
+ * Per step t the linear term of the structured solve is
+ *   w_t = w + Wr r_t      (w = data->w, NULL = 0: shared or per instance; r_t = ref[b, t, :])
+ * so a reference enters exactly as a per-instance data->w would (for F5 only the theta block of
+ * stage N is non-zero: -2 [0 0 LAMBDA]' T, costFunction.m:261).  With nr = 0 every step solves
+ * `data` as it is.  Plant BQP_PLANT_LINEAR:
+ *   x+ = x_eq + Ap (x - x_eq) + Bp (u - u_eq) + d_t     (d_t = dist[b, t, :])
+ * for any (nx, nu, np) the structured solve accepts; cl->delta is not used.  Ap, Bp and dist
+ * belong to that plant alone: with the MG plants (nx = 4, nu = 1) a non-NULL one is BQP_E_ARG.
+ * Otherwise as bqp_closed_loop_ocp: data->x0 is ignored (and may be NULL), a step whose solve
+ * ends != 1 still applies the solver's u_0, the loop's time goes to bqp_last_kernel_ms.
+ * ---------------------------------------------------------------------------------------- */
+#define BQP_PLANT_LINEAR 3
+typedef struct {
+    const double* Ap;  int64_t sAp;    /* nx*nx column-major; NULL = data->A (stride data->sA) */
+    const double* Bp;  int64_t sBp;    /* nx*nu column-major; NULL = data->B (stride data->sB) */
+    const double* dist; int64_t sdist; /* steps*nx per instance, NULL = 0; stride 0 = shared */
+    int nr;                            /* reference dimension (0: no schedule) */
+    const double* Wr;                  /* (N+1)*nv x nr column-major, shared */
+    const double* ref; int64_t sref;   /* steps*nr per instance; stride 0 = one schedule */
+    double* THETA;                     /* out, may be NULL: batch*steps*np, the theta of every
+                                          step's solve (art_refHistory up to Mtheta) */
+} bqp_track;
+
+int bqp_closed_loop_track(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* data,
+                          const bqp_options* opt, const bqp_closed_loop* cl, const bqp_track* tr,
+                          const double* x_init, double* X, double* U, int* exitflag);
+int bqp_closed_loop_track_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
+                                 const bqp_ocp_data* data, const bqp_options* opt,
+                                 const bqp_closed_loop* cl, const bqp_track* tr,
+                                 const double* x_init, double* X, double* U, int* exitflag,
+                                 void* stream);
 
 /* Timing of the most recent solve on this handle: kernel time measured with hipEvents on the
  * launch stream (ms), and the number of kernel launches it covered. */

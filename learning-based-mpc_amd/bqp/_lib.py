@@ -62,6 +62,12 @@ class SqpLoop(C.Structure):
     _fields_ = [('bin0', _PD), ('Bx', _PD), ('warm', C.c_int), ('Z', _PD), ('iterations', _PI)]
 
 
+class Track(C.Structure):
+    _fields_ = [('Ap', _PD), ('sAp', C.c_int64), ('Bp', _PD), ('sBp', C.c_int64),
+                ('dist', _PD), ('sdist', C.c_int64), ('nr', C.c_int), ('Wr', _PD),
+                ('ref', _PD), ('sref', C.c_int64), ('THETA', _PD)]
+
+
 class LbmpcData(C.Structure):
     _fields_ = [(n, _PD) for n in ('A', 'B', 'K', 'Lq', 'Lr', 'Lp', 'Lt', 'LAMBDA', 'PSI', 'xs')] + \
                [('data', _PD), ('sdata', C.c_int64), ('x0', _PD), ('sx0', C.c_int64),
@@ -75,7 +81,7 @@ EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'b
            'bqp_nw_oracle_device', 'bqp_lbmpc_solve_batched', 'bqp_lbmpc_solve_batched_device',
            'bqp_closed_loop_ocp', 'bqp_closed_loop_ocp_device', 'bqp_closed_loop_lbmpc',
            'bqp_closed_loop_lbmpc_device', 'bqp_closed_loop_sqp', 'bqp_closed_loop_sqp_device',
-           'bqp_debug_mixed_flags']
+           'bqp_closed_loop_track', 'bqp_closed_loop_track_device', 'bqp_debug_mixed_flags']
 
 _lib = None
 
@@ -141,6 +147,12 @@ def load():
                                                C.POINTER(LbmpcData), C.POINTER(SqpLoop),
                                                C.POINTER(Options), C.c_void_p, C.c_void_p, _PD,
                                                _PD, _PD, _PI, C.c_void_p]
+    lib.bqp_closed_loop_track.argtypes = [C.c_void_p, C.POINTER(OcpDims), C.c_int, C.POINTER(OcpData),
+                                          C.POINTER(Options), C.c_void_p, C.POINTER(Track), _PD,
+                                          _PD, _PD, _PI]
+    lib.bqp_closed_loop_track_device.argtypes = [C.c_void_p, C.POINTER(OcpDims), C.c_int,
+                                                 C.POINTER(OcpData), C.POINTER(Options), C.c_void_p,
+                                                 C.POINTER(Track), _PD, _PD, _PD, _PI, C.c_void_p]
     _lib = lib
     return lib
 

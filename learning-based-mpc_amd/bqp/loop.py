@@ -5,17 +5,20 @@ repeat - for a whole batch of initial states at once.
 Reference: ``examples/DMS_tracking_LMPC_casadi.m:153-189`` / ``DSS_tracking_LMPC_casadi.m``
 (``solver(...)`` then ``xmeasure = dynamic(delta, xmeasure, u_OL(1:m))``), with the
 Moore-Greitzer plant ``system`` (:215-221) integrated by one RK4 step (``dynamic``, :297-304).
+With a reference schedule and / or a linear plant (bqp_closed_loop_track):
+``trackingMPC/RunExample.m:131-147`` and ``RunExample_robust.m``.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
-from .ocp import OcpResult, _default_handle, pack
+from .ocp import OcpResult, _cm, _default_handle, pack
 
 BQP_PLANT_MG_RK4 = 1
 BQP_PLANT_MG_ODE23 = 2
-_PLANTS = {'rk4': BQP_PLANT_MG_RK4, 'ode23': BQP_PLANT_MG_ODE23}
+BQP_PLANT_LINEAR = 3
+_PLANTS = {'rk4': BQP_PLANT_MG_RK4, 'ode23': BQP_PLANT_MG_ODE23, 'linear': BQP_PLANT_LINEAR}
 
 
 class ClosedLoop(C.Structure):
@@ -33,7 +36,9 @@ class _Dev:
     structure moved to the GPU (each pointer field replaced by a device copy of the numpy array it
     pointed to) and the outputs allocated there, so that the _device entry points run on device
     memory and the trajectories stay in HBM for bqp.dist.gather_rows (RCCL all-gather) - no host
-    round trip between the loop and the collective."""
+    round trip between the loop and the collective.  torch brings its own copy of the HIP runtime:
+    a process that uses device= lets torch open the GPU (torch.cuda.is_available()) before its
+    first bqp call, as smoke() and bench.py do - opened after libbqp's, torch's copy finds no GPU."""
 
     def __init__(self, device):
         import torch
@@ -75,7 +80,7 @@ class _Dev:
 
 
 def closed_loop(mpc, x_init, steps, delta=0.01, handle=None, learning=None, plant='rk4',
-                x_eq=None, u_eq=None, device=None, **opts):
+                x_eq=None, u_eq=None, device=None, refs=None, dist=None, plant_model=None, **opts):
     """mpc: a TrackingLMPC / TrackingLBMPC (deviation coordinates around mpc.x_eq, mpc.u_eq), or
     an LMPC with the working point passed as x_eq / u_eq (functions/ocpLMPC.m: x_wp, u_wp);
     x_init (batch, n) absolute initial states.  Returns X (batch, steps+1, n), U (batch, steps,
@@ -92,12 +97,30 @@ def closed_loop(mpc, x_init, steps, delta=0.01, handle=None, learning=None, plan
 
     device (a GPU index or torch device): run on device memory through the _device entry points
     (bqp_closed_loop_ocp_device / _lbmpc_device) on torch's current stream of that device; the
-    results are torch tensors there (the trajectories stay in HBM, e.g. for bqp.dist.gather_rows)."""
+    results are torch tensors there (the trajectories stay in HBM, e.g. for bqp.dist.gather_rows).
+
+    Reference schedules and linear plants (bqp_closed_loop_track: trackingMPC/RunExample.m:131-147
+    and RunExample_robust.m) - any of the following, or an mpc without a working point (a
+    TrackingMPC; the working point is then zero), selects that loop, which also returns theta
+    (batch, steps, p), the artificial steady state of every step (art_refHistory = Mtheta theta):
+    refs (steps, nr) or (batch, steps, nr): the reference of every step, mapped to the solve's
+    linear term by mpc.reference_map() (TrackingMPC: xs = set_ref(k); TrackingLMPC / LBMPC: the
+    set-point in deviation from x_eq);
+    plant='linear': x+ = x_eq + Ap (x - x_eq) + Bp (u - u_eq) + d_t (getTransitions.m) with
+    plant_model=(Ap, Bp), each shared or per instance (default: the MPC's own A, B), and
+    dist (steps, n) or (batch, steps, n), the additive disturbance d_t (default: none)."""
     lib = _lib.load()
     h = handle or _default_handle()
     x_init = np.ascontiguousarray(np.atleast_2d(x_init), dtype=np.float64)
     b = x_init.shape[0]
     prob = mpc.prob
+    no_wp = x_eq is None and not hasattr(mpc, 'x_eq')
+    if plant == 'linear' or no_wp or any(v is not None for v in (refs, dist, plant_model)):
+        if learning is not None:
+            raise ValueError('closed_loop: learning= does not combine with refs / dist / '
+                             'plant_model / plant=\'linear\'')
+        return _closed_loop_track(lib, h, mpc, x_init, b, int(steps), delta, plant, x_eq, u_eq,
+                                  device, refs, dist, plant_model, opts)
     xeq = np.ascontiguousarray(mpc.x_eq if x_eq is None else np.ravel(x_eq), dtype=np.float64)
     ueq = np.ascontiguousarray(mpc.u_eq if u_eq is None else np.ravel(u_eq), dtype=np.float64)
     dims, data, batch, keep = pack(prob, x_init - xeq)
@@ -153,6 +176,84 @@ def _closed_loop_device(lib, h, mpc, dims, data, keep, cl, wp, x_init, b, steps,
     _lib.check(rc, 'bqp_closed_loop_lbmpc_device')
     d.torch.cuda.current_stream(d.dev).synchronize()
     return OcpResult(X=X, U=U, exitflag=flags, XL=XL, window=win)
+
+
+def _shared_or_batch(a, b, shape, name):
+    """a of the given shape (one copy for the batch) or (batch,) + shape: the contiguous array and
+    its element stride between instances (0 = shared)"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape == tuple(shape):
+        return a, 0
+    if a.shape == (b,) + tuple(shape):
+        return a, int(np.prod(shape))
+    raise ValueError('%s: shape %s, expected %s or %s' % (name, a.shape, tuple(shape), (b,) + tuple(shape)))
+
+
+def _closed_loop_track(lib, h, mpc, x_init, b, steps, delta, plant, x_eq, u_eq, device, refs, dist,
+                       plant_model, opts):
+    """bqp_closed_loop_track(_device): the closed loop with a reference schedule and / or the
+    linear plant (see closed_loop)"""
+    prob = mpc.prob
+    nx, nu, npar = prob.nx, prob.nu, prob.np
+    xeq = np.ascontiguousarray(getattr(mpc, 'x_eq', np.zeros(nx)) if x_eq is None else np.ravel(x_eq),
+                               dtype=np.float64)
+    ueq = np.ascontiguousarray(getattr(mpc, 'u_eq', np.zeros(nu)) if u_eq is None else np.ravel(u_eq),
+                               dtype=np.float64)
+    if plant != 'linear' and (dist is not None or plant_model is not None):
+        raise ValueError("closed_loop: dist= and plant_model= belong to plant='linear'")
+    dims, data, _, keep = pack(prob, x_init - xeq)
+    cl = ClosedLoop(_PLANTS[plant], steps, float(delta), _lib.ptr(xeq), _lib.ptr(ueq))
+    tr = _lib.Track()
+    arrays = []
+    if plant_model is not None:
+        Ap, sAp = _shared_or_batch(_cm(np.asarray(plant_model[0], float)), b, (nx, nx), 'plant_model[0]')
+        Bp, sBp = _shared_or_batch(_cm(np.asarray(plant_model[1], float)), b, (nu, nx), 'plant_model[1]')
+        tr.Ap, tr.sAp, tr.Bp, tr.sBp = _lib.ptr(Ap), sAp, _lib.ptr(Bp), sBp
+        arrays += [Ap, Bp]
+    if dist is not None:
+        dd, tr.sdist = _shared_or_batch(dist, b, (steps, nx), 'dist')
+        tr.dist = _lib.ptr(dd)
+        arrays.append(dd)
+    if refs is not None:
+        Wr = np.asarray(mpc.reference_map(), float)
+        nr = Wr.shape[1]
+        Wc = np.ascontiguousarray(Wr.T)                  # column-major (N+1)*nv x nr
+        rr, tr.sref = _shared_or_batch(refs, b, (steps, nr), 'refs')
+        tr.nr, tr.Wr, tr.ref = nr, _lib.ptr(Wc), _lib.ptr(rr)
+        arrays += [Wc, rr]
+    o = _lib.options(**opts)
+    if device is None:
+        X = np.zeros((b, steps + 1, nx)); U = np.zeros((b, steps, nu))
+        theta = np.zeros((b, steps, npar)); flags = np.zeros((b, steps), np.int32)
+        tr.THETA = _lib.ptr(theta)
+        rc = lib.bqp_closed_loop_track(h.value, C.byref(dims), b, C.byref(data), C.byref(o),
+                                       C.byref(cl), C.byref(tr), _lib.ptr(x_init), _lib.ptr(X),
+                                       _lib.ptr(U), _lib.iptr(flags))
+        _lib.check(rc, 'bqp_closed_loop_track')
+        lo, hi = getattr(mpc, 'xlb0', None), getattr(mpc, 'xub0', None)
+    else:
+        d = _Dev(device)
+        d.inputs(data, keep)
+        d.inputs(cl, [xeq, ueq])
+        d.inputs(tr, arrays)
+        xi = d.array(x_init)
+        X = d.out((b, steps + 1, nx)); U = d.out((b, steps, nu))
+        theta = d.out((b, steps, npar)); flags = d.out((b, steps), np.int32)
+        tr.THETA = d.p(theta)
+        rc = lib.bqp_closed_loop_track_device(h.value, C.byref(dims), b, C.byref(data), C.byref(o),
+                                              C.byref(cl), C.byref(tr), d.p(xi), d.p(X), d.p(U),
+                                              d.p(flags), d.stream())
+        _lib.check(rc, 'bqp_closed_loop_track_device')
+        d.torch.cuda.current_stream(d.dev).synchronize()
+        lo, hi = (d.array(v) if v is not None else None
+                  for v in (getattr(mpc, 'xlb0', None), getattr(mpc, 'xub0', None)))
+    if lo is not None:
+        # TrackingMPC: the constant rows on x_0 (constraintsFunction.m, k = 1) are checked on the
+        # host, as TrackingMPC.solve does: a measured state outside them makes the step's
+        # problem infeasible
+        xm = X[:, :steps]
+        flags[((xm > hi + 1e-12) | (xm < lo - 1e-12)).any(2)] = -2
+    return OcpResult(X=X, U=U, exitflag=flags, theta=theta)
 
 
 def closed_loop_sqp(mpc, x_init, steps, learning=None, warm=True, delta=0.01, handle=None,

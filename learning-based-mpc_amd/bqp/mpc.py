@@ -45,6 +45,14 @@ def _tracking_blocks(n, m, p, LAMBDA, PSI):
     return Ex, Eu, Eth
 
 
+def _reference_map(N, nv, Eth, T):
+    """Wr ((N+1)*nv, n) of a tracking cost |LAMBDA th - r|_T^2: the linear term of reference r is
+    w = Wr r, non-zero only in the theta block of stage N (-2 Eth' T)."""
+    Wr = np.zeros((N + 1, nv, Eth.shape[0]))
+    Wr[N] = -2 * (Eth.T @ T)
+    return Wr.reshape((N + 1) * nv, Eth.shape[0])
+
+
 def _poly(F_T, n, m, p):
     F_T = np.asarray(F_T, float)
     Fp = np.zeros((F_T.shape[0], n + m + p))
@@ -132,6 +140,13 @@ class TrackingLMPC:
         self.x_eq = np.asarray(x_eq, float).ravel()
         self.u_eq = np.atleast_1d(np.asarray(u_eq, float)).ravel()
         self.N, self.n, self.m, self.p = N, n, m, p
+        self.T, self.Eth = Tm, Eth
+
+    def reference_map(self):
+        """Wr ((N+1)*nv, n): the linear term w = Wr r that moves the set-point of the terminal
+        offset cost from x_eq to x_eq + r (terminalcosts :248-251 with r in place of 0; r in
+        deviation coordinates), for closed_loop(..., refs=...)."""
+        return _reference_map(self.N, self.n + self.m + self.p, self.Eth, self.T)
 
     def solve(self, xmeasure, **kw):
         """xmeasure: (batch, n) absolute states.  Returns y_OL (batch, (N+1)n + Nm + p) in the
@@ -202,10 +217,16 @@ class TrackingMPC:
                                Fp=_poly(F_w_N, n, m, p), hp=h_w_N, poly_stage=N)
         self.N, self.n, self.m, self.p = N, n, m, p
 
+    def reference_map(self):
+        """Wr ((N+1)*nv, n): the linear term of reference xs is w = Wr xs (costFunction.m:261),
+        for linear_terms and closed_loop(..., refs=...)."""
+        return _reference_map(self.N, self.n + self.m + self.p, self.Eth, self.T)
+
     def linear_terms(self, xs):
         xs = np.atleast_2d(xs)
-        w = np.zeros((xs.shape[0], self.N + 1, self.n + self.m + self.p))
-        w[:, self.N, :] = -2 * (self.Eth.T @ self.T @ xs.T).T
+        nv = self.n + self.m + self.p
+        w = np.zeros((xs.shape[0], self.N + 1, nv))
+        w[:, self.N, :] = (self.reference_map()[self.N * nv:] @ xs.T).T
         const = np.einsum('bi,ij,bj->b', xs, self.T, xs)
         return w, const
 

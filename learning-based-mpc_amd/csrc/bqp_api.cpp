@@ -1033,6 +1033,134 @@ int bqp_closed_loop_lbmpc(bqp_handle h, const bqp_ocp_dims* d, int batch, const 
 }
 
 // ------------------------------------------------------------------------------------------
+// closed loop with a reference schedule and a linear plant: batched structured solve at
+// w_t = w + Wr r_t, then one advance launch (record, plant step, w_{t+1}), per time step
+// ------------------------------------------------------------------------------------------
+// everything the two entry points take, checked before any buffer is sized from it.  data->x0 is
+// not read by the loop: the check of the problem runs with the initial states in its place
+static int track_check(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D,
+                       const bqp_closed_loop* cl, const bqp_track* tr, const double* x_init,
+                       const double* X, const double* U) {
+    if (!h || !D || !cl || !tr || !x_init || !X || !U) return BQP_E_ARG;
+    bqp_ocp_data Dc = *D;
+    Dc.x0 = x_init;
+    BQP_TRY(ocp_check(d, batch, &Dc));
+    if (cl->steps <= 0 || !cl->x_eq || !cl->u_eq) return BQP_E_ARG;
+    if (cl->plant == BQP_PLANT_LINEAR) {
+        if (tr->sAp < 0 || tr->sBp < 0 || tr->sdist < 0) return BQP_E_ARG;
+    } else if (cl->plant == BQP_PLANT_MG_RK4 || cl->plant == BQP_PLANT_MG_ODE23) {
+        if (tr->Ap || tr->Bp || tr->dist || !(cl->delta > 0)) return BQP_E_ARG;
+        if (d->nx != 4 || d->nu != 1) return BQP_E_UNSUPPORTED;
+    } else {
+        return BQP_E_ARG;
+    }
+    if (tr->nr < 0 || tr->sref < 0) return BQP_E_ARG;
+    if (tr->nr > 0 && (!tr->Wr || !tr->ref)) return BQP_E_ARG;
+    if (D->w && D->sw < 0) return BQP_E_ARG;
+    return BQP_OK;
+}
+
+static int track_impl(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D,
+                      const bqp_options* opt, const bqp_closed_loop* cl, const bqp_track* tr,
+                      const double* x_init, double* X, double* U, int* exitflag, void* stream) {
+    BQP_TRY(track_check(h, d, batch, D, cl, tr, x_init, X, U));
+    DevScope ds(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int nx = d->nx, nu = d->nu, np = d->np, N = d->N;
+    const size_t nw = (size_t)(N + 1) * (nx + nu + np);
+    const bool sched = tr->nr > 0;
+    const layout::CworkTrack CL(batch, nx, nu, np, N, sched ? nw : 0);
+    HIP_TRY(h->cwork.reserve(CL.bytes));
+    bqp::TrackArgs a;
+    memset(&a, 0, sizeof(a));
+    a.batch = batch; a.nx = nx; a.nu = nu; a.np = np; a.N = N; a.steps = cl->steps; a.nr = tr->nr;
+    a.plant = cl->plant; a.delta = cl->delta; a.nw = (int64_t)nw;
+    a.s = layout::at<double>(h->cwork.p, CL.s);
+    double* xo = layout::at<double>(h->cwork.p, CL.x);
+    double* uo = layout::at<double>(h->cwork.p, CL.u);
+    double* th = layout::at<double>(h->cwork.p, CL.theta);
+    int* fl = layout::at<int>(h->cwork.p, CL.flags);
+    a.uo = uo; a.th = th; a.fl = fl;
+    a.w = layout::at<double>(h->cwork.p, CL.w);
+    a.xeq = cl->x_eq; a.ueq = cl->u_eq;
+    a.A = tr->Ap ? tr->Ap : D->A; a.sA = tr->Ap ? tr->sAp : D->sA;
+    a.B = tr->Bp ? tr->Bp : D->B; a.sB = tr->Bp ? tr->sBp : D->sB;
+    a.dist = tr->dist; a.sdist = tr->sdist;
+    a.wbase = D->w; a.swbase = D->sw;
+    a.Wr = tr->Wr; a.ref = tr->ref; a.sref = tr->sref;
+    a.X = X; a.U = U; a.THETA = tr->THETA; a.flags = exitflag;
+    HIP_TRY(bqp::launch_closed_loop_init(batch, nx, cl->steps, x_init, cl->x_eq, a.s, X, st));
+    bqp_ocp_data Dm = *D;
+    Dm.x0 = a.s;
+    Dm.sx0 = nx;
+    if (sched) {   // the solve reads the loop's own linear terms; the init launch forms w_0
+        Dm.w = a.w;
+        Dm.sw = (int64_t)nw;
+        HIP_TRY(bqp::launch_track_advance(a, -1, st));
+    }
+    EventGuard e0;
+    HIP_TRY(hipEventCreate(&e0.e));
+    HIP_TRY(hipEventRecord(e0.e, st));
+    int launches = 0;
+    for (int t = 0; t < cl->steps; ++t) {
+        BQP_TRY(bqp_solve_ocp_batched_device(h, d, batch, &Dm, opt, xo, uo, th, nullptr, fl, nullptr,
+                                             nullptr, stream));
+        launches += h->launches + 1;
+        HIP_TRY(bqp::launch_track_advance(a, t, st));
+    }
+    // timing of the whole loop (solves + advance launches) on this stream
+    HIP_TRY(hipEventRecord(h->ev1, st));
+    HIP_TRY(hipEventSynchronize(h->ev1));
+    std::swap(h->ev0, e0.e);   // the guard destroys the previous start event
+    h->timed = true;
+    h->launches = launches;
+    return BQP_OK;
+}
+
+int bqp_closed_loop_track_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
+                                 const bqp_ocp_data* D, const bqp_options* opt,
+                                 const bqp_closed_loop* cl, const bqp_track* tr,
+                                 const double* x_init, double* X, double* U, int* exitflag,
+                                 void* stream) {
+    return track_impl(h, d, batch, D, opt, cl, tr, x_init, X, U, exitflag, stream);
+}
+
+int bqp_closed_loop_track(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D,
+                          const bqp_options* opt, const bqp_closed_loop* cl, const bqp_track* tr,
+                          const double* x_init, double* X, double* U, int* exitflag) {
+    // validate the whole description before sizing the staging buffers from it
+    BQP_TRY(track_check(h, d, batch, D, cl, tr, x_init, X, U));
+    DevScope ds(h->device);
+    const size_t B = batch, S = cl->steps, nx = d->nx, nu = d->nu, np = d->np;
+    const size_t nw = (size_t)(d->N + 1) * (nx + nu + np), nr = tr->nr;
+    const bool linear = cl->plant == BQP_PLANT_LINEAR;
+    Stage st(h);
+    bqp_ocp_data Dd;
+    bqp_closed_loop cd = *cl;
+    bqp_track td = *tr;
+    double *Xd, *Ud;
+    int* Fd;
+    // Dd.x0: the initial states (a placeholder: the loop feeds the measured states)
+    stage_ocp_data(st, d, batch, D, x_init, B * nx, &Dd);
+    st.in(&cd.x_eq, cl->x_eq, nx);
+    st.in(&cd.u_eq, cl->u_eq, nu);
+    st.in(&td.Ap, linear ? tr->Ap : nullptr, span(batch, tr->sAp, nx * nx));
+    st.in(&td.Bp, linear ? tr->Bp : nullptr, span(batch, tr->sBp, nx * nu));
+    st.in(&td.dist, linear ? tr->dist : nullptr, span(batch, tr->sdist, S * nx));
+    st.in(&td.Wr, tr->Wr, nw * nr);
+    st.in(&td.ref, tr->ref, span(batch, tr->sref, S * nr));
+    st.out(&Xd, B * (S + 1) * nx, X);
+    st.out(&Ud, B * S * nu, U);
+    td.THETA = nullptr;
+    if (tr->THETA) st.out(&td.THETA, B * S * np, tr->THETA);
+    st.out(&Fd, B * S, exitflag);
+    BQP_TRY(st.commit());
+    BQP_TRY(track_impl(h, d, batch, &Dd, opt, &cd, &td, Dd.x0, Xd, Ud, exitflag ? Fd : nullptr,
+                       h->stream));
+    return st.finish();
+}
+
+// ------------------------------------------------------------------------------------------
 // learned-model NLP closed loop: batched SQP + true-plant step + data window, per time step
 // ------------------------------------------------------------------------------------------
 static int sqp_loop_check(const bqp_lbmpc_dims* d, int batch, const bqp_lbmpc_data* D,

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bqp_track.h"
+
 namespace bqp {
 
 // per-instance exit statistics written by every solve kernel and turned into bqp_output by
@@ -160,6 +162,10 @@ hipError_t launch_closed_loop_init(int batch, int nx, int steps, const double* x
 hipError_t launch_mg_plant(int plant, int batch, int N, int steps, int t, double delta,
                            const double* uo, const int* fl, const double* xeq, const double* ueq,
                            double* s, double* X, double* U, int* flags, hipStream_t st);
+// closed loop with a reference schedule (bqp_closed_loop_track; TrackArgs: bqp_track.h): after
+// the step-t solve, record it, step the plant and form the linear terms of step t + 1; t = -1
+// forms those of step 0 alone
+hipError_t launch_track_advance(const TrackArgs& a, int t, hipStream_t st);
 // learned-model NLP closed loop glue (bqp_closed_loop_sqp): per instance bin = bin0 + Bx s and
 // the warm start (z shifted one stage, zero last move, theta kept) before the SQP; u_0 = K s + z_0
 // for the plant, and the step's z / iteration count into the caller's logs after it

@@ -125,6 +125,21 @@ struct CworkOcp : Arena {
     }
 };
 
+// cwork of the closed loop with a reference schedule (bqp_closed_loop_track): measured state, the
+// step's solution (x, u, theta), the step's linear term w_t = w + Wr r_t (nw = (N+1) nv doubles
+// per instance; nw = 0 without a schedule) and exit flags
+struct CworkTrack : Arena {
+    Region s, x, u, theta, w, flags;
+    CworkTrack(size_t B, size_t nx, size_t nu, size_t np, size_t N, size_t nw) {
+        s = take<double>(B * nx);
+        x = take<double>(B * (N + 1) * nx);
+        u = take<double>(B * N * nu);
+        theta = take<double>(B * np);
+        w = take<double>(B * nw);
+        flags = take<int>(B);
+    }
+};
+
 // cwork of the learned-model SQP loop: measured state, SQP iterate (n), the step's constraint rhs
 // (m), first input, window; exit flags, SQP iteration counts, and the asynchronous loop's step
 // counters.  nfin follows ts directly: one memset zeroes both

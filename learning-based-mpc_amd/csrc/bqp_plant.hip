@@ -12,6 +12,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "../../include/bqp.h"
 #include "bqp_internal.h"
 
@@ -154,6 +156,51 @@ __global__ void mg_plant_kernel(int plant, int batch, int N, int steps, int t, d
     }
     U[(int64_t)b * steps + t] = u;
     if (flags) flags[(int64_t)b * steps + t] = fl[b];
+}
+
+// ------------------------------------------------------------------------------------------
+// closed loop with a reference schedule (bqp_closed_loop_track_device): one launch per control
+// step after the solve.  Thread i < batch records the step-t solve of instance i (u_0, theta, exit
+// flag) and steps its plant: the linear plant of trackingMPC/getTransitions.m with per-instance
+// model and disturbance (bqp_track.h), or the Moore-Greitzer plant exactly as mg_plant_kernel
+// steps it.  Thread i < batch * nw forms entry i of the next step's linear terms
+// w_{t+1} = w + Wr r_{t+1}, so consecutive lanes write consecutive entries of one instance's w.
+// The two parts read and write disjoint arrays.  t = -1 (the init launch) only forms w_0.
+// ------------------------------------------------------------------------------------------
+constexpr int TRACK_THREADS = 128;
+
+__global__ void __launch_bounds__(TRACK_THREADS) track_advance_kernel(TrackArgs a, int t) {
+    const int64_t i = (int64_t)blockIdx.x * TRACK_THREADS + threadIdx.x;
+    if (t >= 0 && i < a.batch) {
+        const int b = (int)i;
+        track_record(a, b, t);
+        if (a.plant == BQP_PLANT_LINEAR) {
+            track_linear_step(a, b, t);
+        } else {
+            double x[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[k] = a.s[(int64_t)b * 4 + k] + a.xeq[k];
+            const double u = a.uo[(int64_t)b * a.N] + a.ueq[0];
+            if (a.plant == BQP_PLANT_MG_ODE23) mg_ode23(a.delta, x, u);
+            else mg_rk4(a.delta, x, u);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                a.s[(int64_t)b * 4 + k] = x[k] - a.xeq[k];
+                a.X[track_x_at(a, b, t + 1) + k] = x[k];
+            }
+        }
+    }
+    if (a.nr > 0 && t + 1 < a.steps && i < (int64_t)a.batch * a.nw) track_w_entry(a, i, t + 1);
+}
+
+hipError_t launch_track_advance(const TrackArgs& a, int t, hipStream_t st) {
+    // the MG branch is written for x[4] and one input
+    if (a.plant != BQP_PLANT_LINEAR && (a.nx != 4 || a.nu != 1)) return hipErrorInvalidValue;
+    const int64_t n = std::max<int64_t>(t >= 0 ? a.batch : 0, a.nr > 0 && t + 1 < a.steps ? (int64_t)a.batch * a.nw : 0);
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(track_advance_kernel, dim3((unsigned)((n + TRACK_THREADS - 1) / TRACK_THREADS)),
+                       dim3(TRACK_THREADS), 0, st, a, t);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------
