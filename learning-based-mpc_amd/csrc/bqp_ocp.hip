@@ -138,6 +138,10 @@ __device__ __forceinline__ float fmar(float a, float b, float c) { return __buil
 // every one of them (no packed fp64 multiply exists).  fp32: written as one fma - left to the
 // compiler, neighbouring entries' products are paired into v_pk_mul_f32 with separate adds, so
 // which products are fused follows how a pass deals its entries out over lanes (stage_wave's G)
+// The Riccati sweeps' multiply-adds read the swept vector as a DPP operand (fmac_rbc, bqp_wave.h)
+// in fp64 only: the forced fused operation is what hipcc emits for fp64 anyway, while it does not
+// fuse every fp32 product of the sweeps, so the fp32 instantiation keeps the plain form and its bits.
+constexpr bool SWEEP_DPP_FMAC = sizeof(real) == 8;
 #ifdef BQP_F32
 #define MADD(acc, a, b) acc = fmar((a), (b), (acc))
 #else
@@ -1133,21 +1137,77 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         // sweeps are issue-bound at one instance per SIMD, and the 3x longer instruction
         // stream cost 9.4k -> 14.6k cycles per iteration)
         {
-            real Acol[NS], Bl[NS][NU];
+            real Bl[NS][NU];
 #pragma unroll
             for (int c = 0; c < NS; ++c) {
-                Acol[c] = Abar(c, li);
 #pragma unroll
                 for (int x = 0; x < NU; ++x) Bl[c][x] = Bbar(c, x);
             }
-            real p[NS];
+            if constexpr (SWEEP_DPP_FMAC) {
+            // fp64: the multiply-adds take the previous accumulator as a DPP operand
+            // (fmac_rbc_chain, bqp_wave.h: lane c of the row is the multiplicand of entry c), so
+            // the vector is never copied out into p[]; the start value is one entry per lane.
+            // Lanes >= NS of a row never feed a lane < NS.
+            const int lx = li;
+            real pv = W[L.pv + N * NS + lx];
+            real Acol[NS];
 #pragma unroll
-            for (int i = 0; i < NS; ++i) p[i] = W[L.pv + N * NS + i];
+            for (int c = 0; c < NS; ++c) Acol[c] = Abar(c, lx);
+            auto phi_b = [&](const real (&kc)[NU], real (&ph)[NS]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int c = 0; c < NS; ++c) {
+                    ph[c] = Acol[c];
+#pragma unroll
+                    for (int x = 0; x < NU; ++x) ph[c] += Bl[c][x] * kc[x];
+                }
+            };
+            auto chain_b = [&](const real (&ph)[NS], real q) __attribute__((always_inline)) {
+                real acc = q;
+                acc = fmac_rbc_chain(acc, pv, ph);
+                pv = acc;
+            };
+            auto store_b = [&](int k) __attribute__((always_inline)) {
+                if (lane < NS) W[L.pv + k * NS + lane] = pv;
+            };
+            auto load_k = [&](int k, real (&kc)[NU]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int x = 0; x < NU; ++x) kc[x] = W[L.K + k * NU * NS + x * NS + lx];
+            };
+            auto load_q = [&](int k, real& q) __attribute__((always_inline)) {
+                q = W[L.qt_xpi + k * NS + lx];
+            };
+            real k0[NU], q0, k1[NU], q1;
+            load_k(N - 1, k0);
+            load_q(N - 1, q0);
+            load_k(max(N - 2, 0), k1);
+            load_q(max(N - 2, 0), q1);
+            auto step_b = [&](int k, const real (&kc)[NU], real q) __attribute__((always_inline)) {
+                real ph[NS];
+                phi_b(kc, ph);
+                chain_b(ph, q);
+                store_b(k);
+            };
+            for (int k = N - 1; k >= 1; k -= 2) {
+                step_b(k, k0, q0);
+                load_k(max(k - 2, 0), k0);
+                load_q(max(k - 2, 0), q0);
+                step_b(k - 1, k1, q1);
+                load_k(max(k - 3, 0), k1);
+                load_q(max(k - 3, 0), q1);
+            }
+            if (N & 1) step_b(0, k0, q0);
+            } else {
+            real Acol[NS];
+#pragma unroll
+            for (int c = 0; c < NS; ++c) Acol[c] = Abar(c, li);
             auto load_b = [&](int k, real (&kc)[NU], real& q) __attribute__((always_inline)) {
                 q = W[L.qt_xpi + k * NS + li];
 #pragma unroll
                 for (int x = 0; x < NU; ++x) kc[x] = W[L.K + k * NU * NS + x * NS + li];
             };
+            real p[NS];
+#pragma unroll
+            for (int i = 0; i < NS; ++i) p[i] = W[L.pv + N * NS + i];
             // The refills are unconditional (the stage index clamped at 0: past the last stage a
             // set is refilled with stage 0 again and not used) and the loop takes whole stage
             // pairs with its only exit at the bottom, the single stage of an odd N after it.  A
@@ -1178,6 +1238,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 load_b(max(k - 3, 0), k1, q1);
             }
             if (N & 1) step_b(0, k0, q0);   // set 0 holds stage 0 (N = 1: from the first load)
+            }
         }
         wave_sync();
         STAMP(11);
@@ -1254,6 +1315,66 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
 #pragma unroll
                 for (int i = 0; i < NS; ++i) W[ods + i] = d[i];
             }
+            real k0[NU][NS], f0, k1[NU][NS], f1;
+            auto load_k = [&](int k, real (&kr)[NU][NS]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int x = 0; x < NU; ++x)
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) kr[x][c] = W[L.K + k * NU * NS + x * NS + c];
+            };
+            if constexpr (SWEEP_DPP_FMAC) {
+            // fp64, as the backward sweep: the previous accumulator is the DPP operand of the
+            // multiply-adds; the start value is entry lx of ds_0 = (0, theta_0 step) per lane
+            const int lx = li;
+            real dv = 0.0;
+#pragma unroll
+            for (int x = 0; x < NP; ++x) dv = (lx == NX + x) ? r0[x] : dv;
+            real Arow[NS], Bli[NU];
+#pragma unroll
+            for (int c = 0; c < NS; ++c) Arow[c] = Abar(lx, c);
+#pragma unroll
+            for (int x = 0; x < NU; ++x) Bli[x] = Bbar(lx, x);
+            auto phi_f = [&](const real (&kr)[NU][NS], real (&ph)[NS]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int c = 0; c < NS; ++c) {
+                    ph[c] = Arow[c];
+#pragma unroll
+                    for (int x = 0; x < NU; ++x) ph[c] += Bli[x] * kr[x][c];
+                }
+            };
+            auto chain_f = [&](const real (&ph)[NS], real f) __attribute__((always_inline)) {
+                real acc = f;
+                acc = fmac_rbc_chain(acc, dv, ph);
+                dv = acc;
+            };
+            auto store_f = [&](int k) __attribute__((always_inline)) {
+                if (lane < NS) W[ods + (k + 1) * NS + lane] = dv;
+            };
+            auto load_fk = [&](int k, real& f) __attribute__((always_inline)) {
+                f = W[L.fv + k * NS + lx];
+            };
+            // unconditional refills (stage index clamped at N - 1) and whole stage pairs, as in
+            // the backward sweep
+            load_k(0, k0);
+            load_fk(0, f0);
+            load_k(min(1, N - 1), k1);
+            load_fk(min(1, N - 1), f1);
+            auto step_f = [&](int k, const real (&kr)[NU][NS], real f) __attribute__((always_inline)) {
+                real ph[NS];
+                phi_f(kr, ph);
+                chain_f(ph, f);
+                store_f(k);
+            };
+            for (int k = 0; k + 1 < N; k += 2) {
+                step_f(k, k0, f0);
+                load_k(min(k + 2, N - 1), k0);
+                load_fk(min(k + 2, N - 1), f0);
+                step_f(k + 1, k1, f1);
+                load_k(min(k + 3, N - 1), k1);
+                load_fk(min(k + 3, N - 1), f1);
+            }
+            if (N & 1) step_f(N - 1, k0, f0);
+            } else {
             real Arow[NS], Bli[NU];
 #pragma unroll
             for (int c = 0; c < NS; ++c) Arow[c] = Abar(li, c);
@@ -1261,17 +1382,13 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             for (int x = 0; x < NU; ++x) Bli[x] = Bbar(li, x);
             auto load_f = [&](int k, real (&kr)[NU][NS], real& f) __attribute__((always_inline)) {
                 f = W[L.fv + k * NS + li];
-#pragma unroll
-                for (int x = 0; x < NU; ++x)
-#pragma unroll
-                    for (int c = 0; c < NS; ++c) kr[x][c] = W[L.K + k * NU * NS + x * NS + c];
+                load_k(k, kr);
             };
-            real k0[NU][NS], f0, k1[NU][NS], f1;
             // unconditional refills (stage index clamped at N - 1) and whole stage pairs, as in
             // the backward sweep
             load_f(0, k0, f0);
             load_f(min(1, N - 1), k1, f1);
-            auto step_f = [&](int k, const real (&kr)[NU][NS], real f) __attribute__((always_inline)) {
+            auto step_f =[&](int k, const real (&kr)[NU][NS], real f) __attribute__((always_inline)) {
                 real acc = f;
 #pragma unroll
                 for (int c = 0; c < NS; ++c) {
@@ -1290,6 +1407,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 load_f(min(k + 3, N - 1), k1, f1);
             }
             if (N & 1) step_f(N - 1, k0, f0);   // set 0 holds stage N - 1
+            }
         }
         wave_sync();
         STAMP(13);

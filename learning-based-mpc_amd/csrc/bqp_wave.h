@@ -180,6 +180,77 @@ __device__ __forceinline__ void rbc_all(T v, T (&p)[NC]) {
     if constexpr (C + 1 < NC) rbc_all<C + 1, NC>(v, p);
 }
 
+// acc += (lane C of this 16-lane row of v) * ph as ONE instruction: v_fmac_f64 is VOP2 on gfx950
+// and takes the DPP operand itself, so a broadcast value that is used once, as a multiplicand,
+// needs no v_mov_b64_dpp and no register of its own.  The same fused multiply-add on the same
+// operands as fma(rbc<C>(v), ph, acc): every bit equal (tests/hip/fmac_rbc_check.hip).  A source
+// lane that is disabled reads as 0 (bound_ctrl:1), as rbc.
+//
+// The compiler's hazard recogniser does not look into inline asm, so the two DPP hazards of
+// gfx9 are the caller's:
+//  - a VGPR written by a VALU instruction needs 2 wait states before a DPP instruction reads it.
+//    FRESH = true puts `s_nop 1` (2 wait states) in front of the multiply-add; it is for the call
+//    whose v may come from the instruction just before it (in the sweeps: the first multiply-add
+//    of a step, which reads the accumulator that the previous step's last one wrote).  The
+//    following calls on the same v have that first one between them and the writer.
+//  - a VALU write of EXEC (v_cmpx) needs 5 wait states before a DPP instruction.  hipcc emits no
+//    v_cmpx for gfx950 in these kernels: a guard changes EXEC with SALU instructions
+//    (s_and_saveexec / s_or, as around the sweeps' guarded store), which carry no such rule.
+//    A caller that writes EXEC from the VALU by hand has to add the wait itself.
+template <int C, bool FRESH = false, typename T>
+__device__ __forceinline__ void fmac_rbc(T& acc, T v, T ph) {
+    static_assert(sizeof(T) == 8, "fmac_rbc: fp64 only (the fp32 sweeps keep rbc + plain products)");
+    static_assert(C >= 0 && C < 16, "fmac_rbc: lane of a 16-lane row");
+    if constexpr (FRESH)
+        asm("s_nop 1\n\t"   // DPP read of a VGPR the previous VALU instruction may have written
+            "v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+            : "+v"(acc) : "v"(v), "v"(ph), "n"(C));
+    else
+        asm("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf bound_ctrl:1"
+            : "+v"(acc) : "v"(v), "v"(ph), "n"(C));
+}
+template <int C, int NC, typename T>
+__device__ __forceinline__ void fmac_rbc_seq(T& acc, T v, const T (&ph)[NC]) {
+    fmac_rbc<C, C == 0>(acc, v, ph[C]);
+    if constexpr (C + 1 < NC) fmac_rbc_seq<C + 1, NC>(acc, v, ph);
+}
+// The chain of a sweep step: returns q + sum_c (lane c of v) * ph[c], the products added in the
+// order c = 0 .. NC-1, v possibly written by the instruction just before.  NC = 4, 5 (the model
+// families' NS) are ONE asm statement that starts with the copy of q into the result register:
+//  - between two asm statements that depend on each other the compiler puts an `s_nop 0` (it
+//    must assume that the first writes part of a register), NC - 1 of them per chain;
+//  - q is a loaded value whose register is refilled while the chain's result is still read by the
+//    next step, so a copy is needed somewhere, and the register allocator put it behind the
+//    previous result or in front of the last multiply-add: on the dependent chain.  Written
+//    here it depends on q alone and issues while the previous step's last result is pending.
+// Hazard: the first multiply-add reads v through DPP and v may be the previous VALU instruction's
+// result, which needs 2 wait states: the copy is one, `s_nop 0` the other.  The later ones have
+// those in between.
+#define BQP_FMAC_RBC(OP, C) \
+    "v_fmac_f64_dpp %0, %2, %" #OP " row_newbcast:" #C " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+#define BQP_CHAIN_HEAD \
+    "v_mov_b64 %0, %1\n\t" \
+    "s_nop 0\n\t"   /* with the copy: 2 wait states between v's writer and the DPP read of v */
+template <int NC, typename T>
+__device__ __forceinline__ T fmac_rbc_chain(T q, T v, const T (&ph)[NC]) {
+    static_assert(sizeof(T) == 8, "fmac_rbc_chain: fp64 only");
+    T acc;
+    if constexpr (NC == 4) {
+        asm(BQP_CHAIN_HEAD BQP_FMAC_RBC(3, 0) BQP_FMAC_RBC(4, 1) BQP_FMAC_RBC(5, 2) BQP_FMAC_RBC(6, 3)
+            : "=&v"(acc) : "v"(q), "v"(v), "v"(ph[0]), "v"(ph[1]), "v"(ph[2]), "v"(ph[3]));
+    } else if constexpr (NC == 5) {
+        asm(BQP_CHAIN_HEAD BQP_FMAC_RBC(3, 0) BQP_FMAC_RBC(4, 1) BQP_FMAC_RBC(5, 2) BQP_FMAC_RBC(6, 3)
+            BQP_FMAC_RBC(7, 4)
+            : "=&v"(acc) : "v"(q), "v"(v), "v"(ph[0]), "v"(ph[1]), "v"(ph[2]), "v"(ph[3]), "v"(ph[4]));
+    } else {
+        acc = q;
+        fmac_rbc_seq<0, NC>(acc, v, ph);   // any other length: one statement per multiply-add
+    }
+    return acc;
+}
+#undef BQP_CHAIN_HEAD
+#undef BQP_FMAC_RBC
+
 template <int CTRL, typename T, int KI, int KO>
 __device__ __forceinline__ void tsum_step(const T (&in)[KI], T (&out)[KO], bool hi) {
 #pragma unroll
