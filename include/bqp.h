@@ -415,6 +415,84 @@ int bqp_closed_loop_track_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
                                  const double* x_init, double* X, double* U, int* exitflag,
                                  void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Nonlinear MPC on the true Moore-Greitzer model: the NLP of
+ *   matlab/LBMPC/examples/DMS_tracking_NMPC_casadi.m:121-126, 225-293
+ * with the states eliminated (single shooting).  Decision z = [u_0 - u_eq, .., u_{N-1} - u_eq;
+ * theta], n = N + 1 (nx = 4, nu = 1, np = 1), N <= 127.
+ *   dynamics    x_{k+1} = dynamic(delta, x_k, u_k): one RK4 step of `system` (:217-223, :286-293),
+ *               the plant BQP_PLANT_MG_RK4 steps; x_0 = the measured state (absolute)
+ *   cost        sum_{k<N} [(x_k - x_eq - LAMBDA th)'(delta Q)(.) + (u_k - u_eq - PSI th)'(delta R)(.)]
+ *               + (x_N - x_eq - LAMBDA th)'P(.) + (LAMBDA th)'T(LAMBDA th)
+ *   rows c(z) <= 0, in this order: for k = 1..N  F_x (x_k - x_eq) - h_x (mx rows), then
+ *               F_u (u_{k-1} - u_eq) - h_u (mu rows); then F_T [x_N - x_eq; theta] - h_T (n_poly
+ *               rows).  m = N (mx + mu) + n_poly: IPOPT's lam_g order without the dynamics rows.
+ * Solved by a Gauss-Newton SQP with an L1 merit function: per iteration the rollout with the
+ * stage Jacobians differentiated through the four RK stages (analytic Jacobian of `system`) and
+ * the forward sensitivities, H = 2 Jr'Jr, f = 2 Jr'e, the sub-problem min 0.5 d'Hd + f'd s.t.
+ * C d <= -c on the dense kernels with the instance's own C, eight trial steps alpha = 2^-t, the
+ * penalty nu <- max(nu, 1.1 max lam), merit phi = J + nu sum max(c, 0).  The second-order terms of
+ * the dynamics are not formed.  functions/ocpNMPC.m (fmincon around an ode23 rollout) is not
+ * covered.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+    int N;        /* horizon, 1..127 */
+    int mx, mu;   /* rows of F_x (<= 32) and F_u (<= 8) */
+    int n_poly;   /* rows of F_T */
+} bqp_nmpc_dims;
+
+typedef struct {
+    const double *Lq, *Lr, *Lp, *Lt;   /* upper-triangular ROW-major factors: Lq'Lq = delta Q (4x4),
+                                          Lr'Lr = delta R (1x1), Lp'Lp = P, Lt'Lt = T (4x4) */
+    const double *LAMBDA, *PSI;        /* 4, 1 */
+    const double *x_eq, *u_eq;         /* 4, 1 */
+    const double *F_x, *h_x;           /* mx*4 column-major, mx */
+    const double *F_u, *h_u;           /* mu, mu */
+    const double *F_T, *h_T;           /* n_poly*5 column-major ([x_N - x_eq; theta]), n_poly */
+    double delta;                      /* RK4 step and running-cost weight (in Lq, Lr) */
+    const double* x0; int64_t sx0;     /* measured states, absolute, 4 per instance */
+} bqp_nmpc_data;
+
+/* Rollout and linearisation at given z (batch*n).  Outputs, each may be NULL: X (batch*(N+1)*4,
+ * absolute), cost (batch), c (batch*m), C (batch*m*n, column-major m x n per instance),
+ * H (batch*n*n, column-major, symmetric), f (batch*n). */
+int bqp_nmpc_linearize(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
+                       const double* z, double* X, double* cost, double* c, double* C, double* H,
+                       double* f);
+int bqp_nmpc_linearize_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                              const bqp_nmpc_data* data, const double* z, double* X, double* cost,
+                              double* c, double* C, double* H, double* f, void* stream);
+
+/* SQP solve.  z (batch*n): in = start, out = solution; lam (batch*m, may be NULL): multipliers
+ * of the rows above; cost (batch, may be NULL); exitflag: 1 converged, 0 iteration limit
+ * (opt->max_iter SQP iterations), -2 sub-problem infeasible, -8 numerical failure (a non-finite
+ * accepted iterate included).  The workspace holds every instance's C (m*n doubles: 1.3 MB at
+ * N = 100 with 616 terminal rows); a batch that does not fit returns BQP_E_HIP.  The sub-problems
+ * are polished only with opt->polish > 0 (modes as bqp_lbmpc_solve_batched): on the warm starts
+ * of the closed loop, which lie on active state rows, the polish can fail.  The _device
+ * variant synchronises its stream while it polls for the batch's convergence. */
+int bqp_nmpc_solve_batched(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                           const bqp_nmpc_data* data, const bqp_options* opt, double* z,
+                           double* lam, double* cost, int* exitflag, int* iterations);
+int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                                  const bqp_nmpc_data* data, const bqp_options* opt, double* z,
+                                  double* lam, double* cost, int* exitflag, int* iterations,
+                                  void* stream);
+
+/* Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states, step
+ * synchronous: the solve at the measured states, the RK4 plant with u_0 (cl->plant must be
+ * BQP_PLANT_MG_RK4, cl->delta the plant's step; data->x0 is ignored), then the warm start - z
+ * shifted one stage with the last move repeated and theta kept.  steps = 0 is allowed and returns
+ * X = x_init.  X (batch*(steps+1)*4), U (batch*steps) absolute; exitflag and iterations
+ * (batch*steps, may be NULL) per solve.  The loop's time goes to bqp_last_kernel_ms. */
+int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
+                         const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,
+                         double* X, double* U, int* exitflag, int* iterations);
+int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                                const bqp_nmpc_data* data, const bqp_options* opt,
+                                const bqp_closed_loop* cl, const double* x_init, double* X,
+                                double* U, int* exitflag, int* iterations, void* stream);
+
 /* Timing of the most recent solve on this handle: kernel time measured with hipEvents on the
  * launch stream (ms), and the number of kernel launches it covered. */
 int bqp_last_kernel_ms(bqp_handle h, double* ms, int* launches);

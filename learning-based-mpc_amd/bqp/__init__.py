@@ -10,6 +10,7 @@ from .mpc import LMPC, TrackingLBMPC, TrackingLMPC, TrackingMPC  # noqa: F401
 from .quadprog import quadprog  # noqa: F401
 from .lbmpc import LBMPC, DMSLBMPC, HybridLBMPC, nw_oracle  # noqa: F401
 from .loop import closed_loop, closed_loop_sqp  # noqa: F401
+from .nmpc import NMPC, closed_loop_nmpc  # noqa: F401
 from . import condense, design, sets  # noqa: F401
 
 __version__ = '0.1.0'

@@ -75,13 +75,25 @@ class LbmpcData(C.Structure):
                 ('bandwidth', C.c_double), ('lambda_', C.c_double)]
 
 
+class NmpcDims(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ('N', 'mx', 'mu', 'n_poly')]
+
+
+class NmpcData(C.Structure):
+    _fields_ = [(n, _PD) for n in ('Lq', 'Lr', 'Lp', 'Lt', 'LAMBDA', 'PSI', 'x_eq', 'u_eq', 'F_x',
+                                   'h_x', 'F_u', 'h_u', 'F_T', 'h_T')] + \
+               [('delta', C.c_double), ('x0', _PD), ('sx0', C.c_int64)]
+
+
 EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'bqp_build_source_sha1',
            'bqp_solve_ocp_batched', 'bqp_solve_ocp_batched_device', 'bqp_quadprog_batched',
            'bqp_quadprog_batched_device', 'bqp_last_kernel_ms', 'bqp_nw_oracle',
            'bqp_nw_oracle_device', 'bqp_lbmpc_solve_batched', 'bqp_lbmpc_solve_batched_device',
            'bqp_closed_loop_ocp', 'bqp_closed_loop_ocp_device', 'bqp_closed_loop_lbmpc',
            'bqp_closed_loop_lbmpc_device', 'bqp_closed_loop_sqp', 'bqp_closed_loop_sqp_device',
-           'bqp_closed_loop_track', 'bqp_closed_loop_track_device', 'bqp_debug_mixed_flags']
+           'bqp_closed_loop_track', 'bqp_closed_loop_track_device', 'bqp_debug_mixed_flags',
+           'bqp_nmpc_linearize', 'bqp_nmpc_linearize_device', 'bqp_nmpc_solve_batched',
+           'bqp_nmpc_solve_batched_device', 'bqp_closed_loop_nmpc', 'bqp_closed_loop_nmpc_device']
 
 _lib = None
 
@@ -153,6 +165,17 @@ def load():
     lib.bqp_closed_loop_track_device.argtypes = [C.c_void_p, C.POINTER(OcpDims), C.c_int,
                                                  C.POINTER(OcpData), C.POINTER(Options), C.c_void_p,
                                                  C.POINTER(Track), _PD, _PD, _PD, _PI, C.c_void_p]
+    lib.bqp_nmpc_linearize.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int, C.POINTER(NmpcData)] + \
+        [_PD] * 7
+    lib.bqp_nmpc_linearize_device.argtypes = lib.bqp_nmpc_linearize.argtypes + [C.c_void_p]
+    lib.bqp_nmpc_solve_batched.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int,
+                                           C.POINTER(NmpcData), C.POINTER(Options), _PD, _PD, _PD,
+                                           _PI, _PI]
+    lib.bqp_nmpc_solve_batched_device.argtypes = lib.bqp_nmpc_solve_batched.argtypes + [C.c_void_p]
+    lib.bqp_closed_loop_nmpc.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int,
+                                         C.POINTER(NmpcData), C.POINTER(Options), C.c_void_p, _PD,
+                                         _PD, _PD, _PI, _PI]
+    lib.bqp_closed_loop_nmpc_device.argtypes = lib.bqp_closed_loop_nmpc.argtypes + [C.c_void_p]
     _lib = lib
     return lib
 

@@ -1,0 +1,136 @@
+"""Nonlinear MPC on the true Moore-Greitzer model: the host-side mirror of the solve call of
+``examples/DMS_tracking_NMPC_casadi.m:163-167`` (CasADi/IPOPT over ``y = [x_0..x_N; u; theta]``
+with the RK4 dynamics as equality rows), mapped onto bqp_nmpc_solve_batched - a single-shooting
+Gauss-Newton SQP with an L1 merit function on the GPU (csrc/bqp_nmpc.hip) - and its closed loop
+(:153-207) onto bqp_closed_loop_nmpc.
+
+The states are eliminated: the decision is ``z = [u - u_eq; theta]`` (n = N + 1).  The rows, and
+the multipliers ``lam``, are in IPOPT's ``lam_g`` order with the dynamics rows removed: per stage
+k = 1..N the rows of F_x then of F_u, then the terminal set.  ``functions/ocpNMPC.m`` (fmincon
+around an ode23 rollout) is not covered.
+
+This module only marshals data; everything iterative runs on the GPU.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .lbmpc import _upper_factor
+from .loop import ClosedLoop
+from .ocp import OcpResult, _default_handle
+
+_BQP_PLANT_MG_RK4 = 1
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+class NMPC:
+    """Tracking NMPC of DMS_tracking_NMPC_casadi.m (absolute coordinates, nx = 4, nu = 1, one
+    artificial-reference parameter theta); N <= 127."""
+
+    def __init__(self, Q, R, P, T, LAMBDA, PSI, F_x, h_x, F_u, h_u, F_w_N, h_w_N, x_eq, u_eq, N,
+                 delta=0.01):
+        self.N, self.n, self.delta = int(N), int(N) + 1, float(delta)
+        Tm = np.asarray(T, float) * np.eye(4) if np.ndim(T) == 0 else np.asarray(T, float)
+        F_x = np.atleast_2d(np.asarray(F_x, float))
+        F_u = np.asarray(F_u, float).reshape(-1, 1)
+        F_T = np.atleast_2d(np.asarray(F_w_N, float))
+        if F_x.shape[1] != 4 or F_T.shape[1] != 5:
+            raise ValueError('F_x has 4 columns and F_w_N 5 ([x_N - x_eq; theta])')
+        self.mx, self.mu, self.mp = F_x.shape[0], F_u.shape[0], F_T.shape[0]
+        self.m = self.N * (self.mx + self.mu) + self.mp
+        self.x_eq = _f64(np.asarray(x_eq, float).ravel())
+        self.u_eq = _f64(np.atleast_1d(np.asarray(u_eq, float)).ravel()[:1])
+        # the arrays the C structure points to (kept alive with the object)
+        self._keep = [_upper_factor(self.delta * np.atleast_2d(Q)),
+                      _upper_factor(self.delta * np.atleast_2d(R)), _upper_factor(P),
+                      _upper_factor(Tm), _f64(np.asarray(LAMBDA, float).ravel()),
+                      _f64(np.asarray(PSI, float).ravel()), self.x_eq, self.u_eq,
+                      _f64(F_x.T), _f64(np.asarray(h_x, float).ravel()),       # column-major
+                      _f64(F_u.ravel()), _f64(np.asarray(h_u, float).ravel()),
+                      _f64(F_T.T), _f64(np.asarray(h_w_N, float).ravel())]
+
+    def _dims(self):
+        return _lib.NmpcDims(self.N, self.mx, self.mu, self.mp)
+
+    def _data(self, x0=None):
+        return _lib.NmpcData(*[_lib.ptr(a) for a in self._keep], self.delta,
+                             _lib.ptr(x0) if x0 is not None else None, 4)
+
+    def _z(self, b, z):
+        if z is None:
+            return np.zeros((b, self.n))
+        return _f64(np.broadcast_to(np.atleast_2d(np.asarray(z, float)), (b, self.n))).copy()
+
+    def linearize(self, xmeasure, z=None, handle=None):
+        """rollout and linearisation at z (batch, N + 1) = [u - u_eq; theta] from the measured
+        states xmeasure (batch, 4), absolute.  Returns X (batch, N + 1, 4), cost (batch,),
+        c (batch, m), C (batch, m, n) = dc/dz, H (batch, n, n) = 2 Jr'Jr, f (batch, n)."""
+        lib = _lib.load()
+        h = handle or _default_handle()
+        x0 = _f64(np.atleast_2d(xmeasure))
+        b, n, m = x0.shape[0], self.n, self.m
+        z = self._z(b, z)
+        X = np.zeros((b, self.N + 1, 4)); cost = np.zeros(b); c = np.zeros((b, m))
+        Ccm = np.zeros((b, n, m)); H = np.zeros((b, n, n)); f = np.zeros((b, n))
+        dims, dd = self._dims(), self._data(x0)
+        rc = lib.bqp_nmpc_linearize(h.value, C.byref(dims), b, C.byref(dd), _lib.ptr(z), _lib.ptr(X),
+                                    _lib.ptr(cost), _lib.ptr(c), _lib.ptr(Ccm), _lib.ptr(H),
+                                    _lib.ptr(f))
+        _lib.check(rc, 'bqp_nmpc_linearize')
+        return OcpResult(X=X, cost=cost, c=c, C=np.swapaxes(Ccm, 1, 2), H=H, f=f)
+
+    def solve(self, xmeasure, y0=None, z0=None, handle=None, max_iter=100, tol=1e-8, polish=0):
+        """xmeasure (batch, 4) absolute states; y0 a start in the script's layout
+        [x_0..x_N; u; theta] (its states are ignored: they follow from u) or z0 = [u - u_eq;
+        theta]; cold start u = u_eq, theta = 0 otherwise.  Returns y_OL (batch, 4 (N + 1) + N + 1)
+        in the script's layout, u0, theta, z, lam (batch, m), cost, exitflag, iterations."""
+        lib = _lib.load()
+        h = handle or _default_handle()
+        x0 = _f64(np.atleast_2d(xmeasure))
+        b, N, n, m = x0.shape[0], self.N, self.n, self.m
+        if y0 is not None:
+            y0 = np.atleast_2d(np.asarray(y0, float))
+            z0 = np.concatenate([y0[:, 4 * (N + 1):4 * (N + 1) + N] - self.u_eq[0], y0[:, -1:]], axis=1)
+        z = self._z(b, z0)
+        lam = np.zeros((b, m)); cost = np.zeros(b)
+        flag = np.zeros(b, np.int32); it = np.zeros(b, np.int32)
+        dims, dd = self._dims(), self._data(x0)
+        o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
+        rc = lib.bqp_nmpc_solve_batched(h.value, C.byref(dims), b, C.byref(dd), C.byref(o),
+                                        _lib.ptr(z), _lib.ptr(lam), _lib.ptr(cost), _lib.iptr(flag),
+                                        _lib.iptr(it))
+        _lib.check(rc, 'bqp_nmpc_solve_batched')
+        r = OcpResult(z=z, lam=lam, cost=cost, exitflag=flag, iterations=it)
+        # the open-loop states of the solution: the rollout the solver itself computes
+        X = np.zeros((b, N + 1, 4))
+        rc = lib.bqp_nmpc_linearize(h.value, C.byref(dims), b, C.byref(dd), _lib.ptr(z), _lib.ptr(X),
+                                    None, None, None, None, None)
+        _lib.check(rc, 'bqp_nmpc_linearize')
+        r.update(y_OL=np.concatenate([X.reshape(b, -1), z[:, :N] + self.u_eq[0], z[:, N:]], axis=1),
+                 u0=z[:, :1] + self.u_eq[0], theta=z[:, N:])
+        return r
+
+
+def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, polish=0):
+    """Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states x_init
+    (batch, 4), absolute: per step the batched solve at the measured states, the RK4 plant with
+    u_0, and the warm start (z shifted one stage, last move repeated, theta kept).  Returns
+    X (batch, steps + 1, 4), U (batch, steps), exitflag and iterations (batch, steps), ms."""
+    lib = _lib.load()
+    h = handle or _default_handle()
+    xi = _f64(np.atleast_2d(x_init))
+    b, steps = xi.shape[0], int(steps)
+    X = np.zeros((b, steps + 1, 4)); U = np.zeros((b, steps))
+    fl = np.zeros((b, steps), np.int32); it = np.zeros((b, steps), np.int32)
+    dims, dd = prob._dims(), prob._data()
+    cl = ClosedLoop(_BQP_PLANT_MG_RK4, steps, prob.delta, _lib.ptr(prob.x_eq), _lib.ptr(prob.u_eq))
+    o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
+    rc = lib.bqp_closed_loop_nmpc(h.value, C.byref(dims), b, C.byref(dd), C.byref(o), C.byref(cl),
+                                  _lib.ptr(xi), _lib.ptr(X), _lib.ptr(U), _lib.iptr(fl), _lib.iptr(it))
+    _lib.check(rc, 'bqp_closed_loop_nmpc')
+    ms, launches = h.kernel_ms()
+    return OcpResult(X=X, U=U, exitflag=fl, iterations=it, kernel_ms=ms, launches=launches)

@@ -48,6 +48,7 @@ struct bqp_handle_s {
     DevBuf stage;  // staging of host-pointer calls
     DevBuf dwork;  // dense per-instance scratch
     DevBuf lwork;  // learning-based MPC (SQP) buffers
+    DevBuf nwork;  // nonlinear MPC (SQP) buffers, every instance's constraint Jacobian included
     DevBuf cwork;  // closed-loop simulation buffers
     DevBuf hwork;  // mixed precision: fp32 -> fp64 handoff records
     DevBuf pwork;  // long-horizon layout: global Riccati tables
@@ -219,6 +220,7 @@ int bqp_destroy(bqp_handle h) {
         h->stage.release();
         h->dwork.release();
         h->lwork.release();
+        h->nwork.release();
         h->cwork.release();
         h->hwork.release();
         h->pwork.release();
@@ -1327,6 +1329,346 @@ int bqp_closed_loop_sqp(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
     sd.iterations = sl->iterations ? Id : nullptr;
     BQP_TRY(bqp_closed_loop_sqp_device(h, d, batch, &Dd, &sd, opt, &cd, &ld, xi, Xd, Ud,
                                        exitflag ? Fd : nullptr, h->stream));
+    return st.finish();
+}
+
+// ------------------------------------------------------------------------------------------
+// nonlinear MPC on the true Moore-Greitzer model: single-shooting Gauss-Newton SQP (bqp_nmpc.hip)
+// ------------------------------------------------------------------------------------------
+static int nmpc_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D, bool need_x0) {
+    if (!d || !D || batch <= 0) return BQP_E_ARG;
+    if (d->N <= 0 || d->mx < 0 || d->mu < 0 || d->n_poly < 0 || !(D->delta > 0)) return BQP_E_ARG;
+    if (!D->Lq || !D->Lr || !D->Lp || !D->Lt || !D->LAMBDA || !D->PSI || !D->x_eq || !D->u_eq ||
+        (d->mx > 0 && (!D->F_x || !D->h_x)) || (d->mu > 0 && (!D->F_u || !D->h_u)) ||
+        (d->n_poly > 0 && (!D->F_T || !D->h_T)) || (need_x0 && !D->x0))
+        return BQP_E_ARG;
+    if (!bqp::nmpc_supported(d->N, d->mx, d->mu)) return BQP_E_UNSUPPORTED;
+    const int64_t m = (int64_t)d->N * (d->mx + d->mu) + d->n_poly;
+    if (m < 1 || m > 8192) return BQP_E_UNSUPPORTED;
+    return BQP_OK;
+}
+
+// the SQP's kernel arguments over the handle's nwork (done, ndone and the penalty zeroed) and
+// the dense-kernel arguments of its sub-problem with the instance's own C; C, H, f: the
+// caller's arrays (the linearisation's outputs) or null for the workspace's
+static hipError_t nmpc_setup(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                             const bqp_options& o, double* C, double* H, double* f, hipStream_t st,
+                             bqp::NmpcArgs& a, bqp::LbmpcArgs& ne, bqp::DenseKernelArgs* q) {
+    const int N = d->N, n = N + 1, m = N * (d->mx + d->mu) + d->n_poly;
+    const size_t B = batch;
+    const layout::Nwork NL(batch, N, m, LB_NTRIAL);
+    hipError_t e = h->nwork.reserve(NL.bytes);
+    if (e != hipSuccess) return e;
+    void* nw = h->nwork.p;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.n = n; a.nr = (int)NL.nr; a.m = m; a.mx = d->mx; a.mu = d->mu; a.mp = d->n_poly;
+    a.batch = batch; a.ntrial = LB_NTRIAL; a.max_iter = o.max_iter;
+    a.delta = D->delta;
+    a.tol_step = o.tol_stat;            // as the learned-model SQP
+    a.tol_stat = 10.0 * o.tol_stat;
+    a.Lq = D->Lq; a.Lr = D->Lr; a.Lp = D->Lp; a.Lt = D->Lt; a.LAM = D->LAMBDA; a.PSI = D->PSI;
+    a.xeq = D->x_eq; a.ueq = D->u_eq; a.Fx = D->F_x; a.hx = D->h_x; a.Fu = D->F_u; a.hu = D->h_u;
+    a.FT = D->F_T; a.hT = D->h_T;
+    a.x0 = D->x0; a.sx0 = D->sx0;
+    a.Jr = layout::at<double>(nw, NL.Jr);
+    a.er = layout::at<double>(nw, NL.er);
+    a.H = H ? H : layout::at<double>(nw, NL.H);
+    a.f = f ? f : layout::at<double>(nw, NL.f);
+    a.C = C ? C : layout::at<double>(nw, NL.C);
+    a.rhs = layout::at<double>(nw, NL.rhs);
+    a.lam = layout::at<double>(nw, NL.lam);
+    a.d = layout::at<double>(nw, NL.d);
+    a.cost0 = layout::at<double>(nw, NL.cost0);
+    a.costT = layout::at<double>(nw, NL.costT);
+    a.violT = layout::at<double>(nw, NL.violT);
+    a.stat = layout::at<double>(nw, NL.stat);
+    a.cprev = layout::at<double>(nw, NL.cprev);
+    a.nu = layout::at<double>(nw, NL.nu);
+    a.qpflag = layout::at<int>(nw, NL.qpflag);
+    a.done = layout::at<int>(nw, NL.done);
+    a.ndone = layout::at<int>(nw, NL.ndone);
+    if ((e = hipMemsetAsync(a.done, 0, sizeof(int) * (B + 1), st)) != hipSuccess) return e;   // done[], ndone
+    if ((e = hipMemsetAsync(a.nu, 0, sizeof(double) * B, st)) != hipSuccess) return e;
+    // normal equations: the learned-model path's kernel on this Jr / er; with m = 0 it forms no
+    // constraint right-hand side and reads neither Ain nor bin
+    memset(&ne, 0, sizeof(ne));
+    ne.N = N; ne.n = n; ne.nr = a.nr; ne.m = 0; ne.batch = batch;
+    ne.Jr = a.Jr; ne.er = a.er; ne.H = a.H; ne.f = a.f; ne.done = a.done;
+    if (!q) return hipSuccess;
+    // QP sub-problem (dense kernel): min 0.5 d'Hd + f'd  s.t.  C d <= -c, C per instance
+    const int64_t wst = bqp::dense_work_doubles(n, m, 0);
+    const layout::Dwork DL(wst, batch, bqp::STATS_W);
+    if ((e = h->dwork.reserve(DL.bytes)) != hipSuccess) return e;
+    bqp_options qo;
+    bqp_default_options(&qo);
+    memset(q, 0, sizeof(*q));
+    q->n = n; q->m = m; q->me = 0; q->batch = batch; q->max_iter = 100;
+    q->tol_stat = qo.tol_stat; q->tol_feas = qo.tol_feas; q->tol_comp = qo.tol_comp; q->tau = qo.tau;
+    q->H = a.H; q->f = a.f; q->A = a.C; q->b = a.rhs;
+    q->sH = (int64_t)n * n; q->sf = n; q->sA = (int64_t)m * n; q->sb = m;
+    q->x = a.d; q->lam_ineqlin = a.lam; q->exitflag = a.qpflag;
+    q->work = layout::at<double>(h->dwork.p, DL.scratch); q->work_stride = wst;
+    q->skip = a.done;
+    q->stats = layout::at<double>(h->dwork.p, DL.stats);
+    return hipSuccess;
+}
+
+int bqp_nmpc_linearize_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                              const bqp_nmpc_data* D, const double* z, double* X, double* cost,
+                              double* c, double* C, double* H, double* f, void* stream) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z) return BQP_E_ARG;
+    DevScope ds(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    bqp_options o;
+    resolve(nullptr, &o);
+    bqp::NmpcArgs a;
+    bqp::LbmpcArgs ne;
+    HIP_TRY(nmpc_setup(h, d, batch, D, o, C, H, f, st, a, ne, nullptr));
+    a.z = const_cast<double*>(z);       // read only by the rollout
+    ne.z = a.z;
+    a.Xout = X; a.cout = c;
+    HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st));
+    if (H || f) HIP_TRY(bqp::launch_lbmpc_normal(ne, st));
+    if (cost) HIP_TRY(hipMemcpyAsync(cost, a.cost0, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
+    return BQP_OK;
+}
+
+// registers the shared problem data of D with the stage; after st.commit() *Dd holds the device
+// copies (x0 is the caller's to set)
+static void stage_nmpc_data(Stage& st, const bqp_nmpc_dims* d, const bqp_nmpc_data* D, bqp_nmpc_data* Dd) {
+    const size_t mx = d->mx, mu = d->mu, mp = d->n_poly;
+    *Dd = *D;
+    st.in(&Dd->Lq, D->Lq, 16);          st.in(&Dd->Lr, D->Lr, 1);
+    st.in(&Dd->Lp, D->Lp, 16);          st.in(&Dd->Lt, D->Lt, 16);
+    st.in(&Dd->LAMBDA, D->LAMBDA, 4);   st.in(&Dd->PSI, D->PSI, 1);
+    st.in(&Dd->x_eq, D->x_eq, 4);       st.in(&Dd->u_eq, D->u_eq, 1);
+    st.in(&Dd->F_x, D->F_x, 4 * mx);    st.in(&Dd->h_x, D->h_x, mx);
+    st.in(&Dd->F_u, D->F_u, mu);        st.in(&Dd->h_u, D->h_u, mu);
+    st.in(&Dd->F_T, D->F_T, 5 * mp);    st.in(&Dd->h_T, D->h_T, mp);
+}
+
+int bqp_nmpc_linearize(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                       const double* z, double* X, double* cost, double* c, double* C, double* H,
+                       double* f) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z) return BQP_E_ARG;
+    DevScope ds(h->device);
+    const size_t B = batch, N = d->N, n = N + 1, m = N * (size_t)(d->mx + d->mu) + d->n_poly;
+    Stage st(h);
+    bqp_nmpc_data Dd;
+    const double* zd;
+    double *Xd = nullptr, *cd = nullptr, *cvd = nullptr, *Cd = nullptr, *Hd = nullptr, *fd = nullptr;
+    stage_nmpc_data(st, d, D, &Dd);
+    st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
+    st.in(&zd, z, B * n);
+    if (X) st.out(&Xd, B * (N + 1) * 4, X);
+    if (cost) st.out(&cd, B, cost);
+    if (c) st.out(&cvd, B * m, c);
+    if (C) st.out(&Cd, B * m * n, C);
+    if (H) st.out(&Hd, B * n * n, H);
+    if (f) st.out(&fd, B * n, f);
+    BQP_TRY(st.commit());
+    BQP_TRY(bqp_nmpc_linearize_device(h, d, batch, &Dd, zd, Xd, cd, cvd, Cd, Hd, fd, h->stream));
+    return st.finish();
+}
+
+int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                                  const bqp_nmpc_data* D, const bqp_options* opt, double* z,
+                                  double* lam, double* cost, int* exitflag, int* iterations,
+                                  void* stream) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z || !exitflag || !iterations) return BQP_E_ARG;
+    DevScope ds(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    bqp_options o;
+    resolve(opt, &o);
+    const size_t B = batch;
+    bqp::NmpcArgs a;
+    bqp::LbmpcArgs ne;
+    bqp::DenseKernelArgs q;
+    HIP_TRY(nmpc_setup(h, d, batch, D, o, nullptr, nullptr, nullptr, st, a, ne, &q));
+    a.z = z; ne.z = z; a.flag = exitflag; a.iters = iterations;
+    if (lam) { a.lam = lam; q.lam_ineqlin = lam; }
+    HIP_TRY(hipMemsetAsync(a.iters, 0, sizeof(int) * B, st));
+    HIP_TRY(hipMemsetAsync(a.flag, 0, sizeof(int) * B, st));
+    HIP_TRY(hipEventRecord(h->ev0, st));
+    int launches = 0;
+    // BQP_LB_TRACE diagnostics on stderr, as the learned-model solve's: 1 the sub-problems' exit
+    // flags per iteration (and whether their steps are finite), 2 per-launch event times instead.
+    // Both wait for the stream at each iteration; neither launches a kernel.
+    const char* tenv = getenv("BQP_LB_TRACE");
+    const bool trace = tenv && atoi(tenv) >= 2, trace_flags = tenv && !trace;
+    EventGuard ev[6];
+    auto mark = [&](int k) -> int {
+        if (!trace) return BQP_OK;
+        if (!ev[k].e) HIP_TRY(hipEventCreate(&ev[k].e));
+        HIP_TRY(hipEventRecord(ev[k].e, st));
+        return BQP_OK;
+    };
+    for (int it = 0; it < o.max_iter; ++it) {
+        // The sub-problems are polished only where the caller asks for it (opt->polish > 0), not by
+        // default as in the learned-model solve.  A warm start of the closed loop lies on the state
+        // rows that were active a step before (x2 at its lower bound in the stored run's
+        // neighbourhood); the Jacobian of such a row of stage 1 w.r.t. u_0 is O(delta^3), the
+        // polish's active-set system is then singular to working precision, and it returned a
+        // non-finite step flagged converged (10 of 280 instance-steps of the perturbed stored run
+        // ended -8 that way).  The interior-point iterate of those sub-problems (exit -8 once
+        // mu ~ 1e-15, which the update kernel takes as is) is accurate: the same solves converge
+        // in 2-3 SQP iterations without the polish.
+        q.polish = o.polish > 0 ? sub_polish(o.polish, it >= LB_POLISH_STALL) : 0;
+        BQP_TRY(mark(0));
+        HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st));
+        BQP_TRY(mark(1));
+        HIP_TRY(bqp::launch_lbmpc_normal(ne, st));
+        BQP_TRY(mark(2));
+        HIP_TRY(bqp::launch_dense(q, st));
+        BQP_TRY(mark(3));
+        if (trace_flags) {
+            std::vector<int> fl(B), dn(B);
+            std::vector<double> dv(B * a.n);
+            HIP_TRY(hipMemcpyAsync(fl.data(), a.qpflag, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(dn.data(), a.done, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(dv.data(), a.d, sizeof(double) * B * a.n, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            for (size_t b = 0; b < B; ++b) {
+                if (dn[b]) continue;
+                double dm = 0.0;
+                for (int j = 0; j < a.n; ++j) dm = std::isfinite(dv[b * a.n + j]) ? std::max(dm, fabs(dv[b * a.n + j])) : INFINITY;
+                fprintf(stderr, "bqp nmpc it %d instance %zu: sub-problem flag %d, |d| %.3e\n", it, b, fl[b], dm);
+            }
+        }
+        HIP_TRY(bqp::launch_nmpc_rollout(a, 0, st));
+        BQP_TRY(mark(4));
+        HIP_TRY(bqp::launch_nmpc_update(a, st));
+        BQP_TRY(mark(5));
+        launches += 5;
+        if (trace) {
+            HIP_TRY(hipEventSynchronize(ev[5].e));
+            float ms[5];
+            for (int j = 0; j < 5; ++j) HIP_TRY(hipEventElapsedTime(&ms[j], ev[j].e, ev[j + 1].e));
+            fprintf(stderr, "bqp nmpc it %d ms: linearise %.3f normal %.3f dense(+polish) %.3f trials %.3f update %.3f\n",
+                    it, ms[0], ms[1], ms[2], ms[3], ms[4]);
+        }
+        // polled as the learned-model solve polls: after each iteration for large sub-problems
+        if ((it + 1) % (a.n >= 64 ? 1 : 4) == 0 || it + 1 == o.max_iter) {
+            int nd_h = 0;
+            HIP_TRY(hipMemcpyAsync(&nd_h, a.ndone, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (nd_h >= batch) break;
+        }
+    }
+    HIP_TRY(hipEventRecord(h->ev1, st));
+    h->timed = true;
+    h->launches = launches;
+    if (cost) HIP_TRY(hipMemcpyAsync(cost, a.cost0, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
+    return BQP_OK;
+}
+
+int bqp_nmpc_solve_batched(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                           const bqp_nmpc_data* D, const bqp_options* opt, double* z,
+                           double* lam, double* cost, int* exitflag, int* iterations) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z || !exitflag || !iterations) return BQP_E_ARG;
+    DevScope ds(h->device);
+    const size_t B = batch, N = d->N, n = N + 1, m = N * (size_t)(d->mx + d->mu) + d->n_poly;
+    Stage st(h);
+    bqp_nmpc_data Dd;
+    double *zd, *ld, *cd;
+    int *ed, *itd;
+    stage_nmpc_data(st, d, D, &Dd);
+    st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
+    st.in(&zd, z, B * n, z);   // the initial iterate, and the solution
+    st.out(&ld, B * m, lam);
+    st.out(&cd, B, cost);
+    st.out(&ed, B, exitflag);
+    st.out(&itd, B, iterations);
+    BQP_TRY(st.commit());
+    BQP_TRY(bqp_nmpc_solve_batched_device(h, d, batch, &Dd, opt, zd, ld, cd, ed, itd, h->stream));
+    return st.finish();
+}
+
+static int nmpc_loop_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                           const bqp_closed_loop* cl, const double* x_init, const double* X,
+                           const double* U) {
+    if (!cl || !x_init || !X) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, false));
+    if (cl->plant != BQP_PLANT_MG_RK4 || cl->steps < 0 || !(cl->delta > 0) || !cl->x_eq || !cl->u_eq ||
+        (cl->steps > 0 && !U))
+        return BQP_E_ARG;
+    return BQP_OK;
+}
+
+int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                                const bqp_nmpc_data* D, const bqp_options* opt,
+                                const bqp_closed_loop* cl, const double* x_init, double* X,
+                                double* U, int* exitflag, int* iterations, void* stream) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_loop_check(d, batch, D, cl, x_init, X, U));
+    DevScope ds(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    const int N = d->N, n = N + 1, S = cl->steps;
+    const size_t B = batch;
+    const layout::CworkNmpc CL(batch, n);
+    HIP_TRY(h->cwork.reserve(CL.bytes));
+    double* s = layout::at<double>(h->cwork.p, CL.s);
+    double* z = layout::at<double>(h->cwork.p, CL.z);
+    int* fl = layout::at<int>(h->cwork.p, CL.flags);
+    int* it = layout::at<int>(h->cwork.p, CL.iters);
+    HIP_TRY(bqp::launch_closed_loop_init(batch, 4, S, x_init, cl->x_eq, s, X, st));
+    HIP_TRY(hipMemsetAsync(z, 0, sizeof(double) * B * n, st));   // cold start: u = u_eq, theta = 0
+    EventGuard e0;
+    HIP_TRY(hipEventCreate(&e0.e));
+    HIP_TRY(hipEventRecord(e0.e, st));
+    int launches = 0;
+    bqp_nmpc_data Dl = *D;
+    Dl.sx0 = (int64_t)(S + 1) * 4;
+    for (int t = 0; t < S; ++t) {
+        Dl.x0 = X + (int64_t)t * 4;      // the measured states X[:, t], absolute
+        BQP_TRY(bqp_nmpc_solve_batched_device(h, d, batch, &Dl, opt, z, nullptr, nullptr, fl, it, stream));
+        launches += h->launches;
+        // the plant reads u_0 - u_eq = z[b, 0] (stride n)
+        HIP_TRY(bqp::launch_mg_plant(cl->plant, batch, n, S, t, cl->delta, z, fl, cl->x_eq, cl->u_eq,
+                                     s, X, U, exitflag, st));
+        HIP_TRY(bqp::launch_nmpc_loop_shift(batch, N, S, t, z, it, iterations, st));
+        launches += 2;
+    }
+    HIP_TRY(hipEventRecord(h->ev1, st));
+    HIP_TRY(hipEventSynchronize(h->ev1));
+    std::swap(h->ev0, e0.e);   // the guard destroys the previous start event
+    h->timed = true;
+    h->launches = launches;
+    return BQP_OK;
+}
+
+int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                         const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,
+                         double* X, double* U, int* exitflag, int* iterations) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_loop_check(d, batch, D, cl, x_init, X, U));
+    DevScope ds(h->device);
+    const size_t B = batch, S = cl->steps;
+    Stage st(h);
+    bqp_nmpc_data Dd;
+    bqp_closed_loop cd = *cl;
+    const double* xi;
+    double *Xd, *Ud;
+    int *Fd, *Id;
+    stage_nmpc_data(st, d, D, &Dd);
+    st.in(&xi, x_init, B * 4);
+    st.in(&cd.x_eq, cl->x_eq, 4);
+    st.in(&cd.u_eq, cl->u_eq, 1);
+    st.out(&Xd, B * (S + 1) * 4, X);
+    st.out(&Ud, B * S, U);
+    st.out(&Fd, B * S, exitflag);
+    st.out(&Id, B * S, iterations);
+    BQP_TRY(st.commit());
+    BQP_TRY(bqp_closed_loop_nmpc_device(h, d, batch, &Dd, opt, &cd, xi, Xd, Ud, exitflag ? Fd : nullptr,
+                                        iterations ? Id : nullptr, h->stream));
     return st.finish();
 }
 

@@ -155,6 +155,36 @@ hipError_t launch_lbmpc_normal(const LbmpcArgs& a, hipStream_t st);
 hipError_t launch_lbmpc_update(const LbmpcArgs& a, hipStream_t st);
 hipError_t launch_lbmpc_hess(const LbmpcArgs& a, hipStream_t st);
 
+// Nonlinear MPC on the true Moore-Greitzer model (single-shooting Gauss-Newton SQP with an L1
+// merit function), bqp_nmpc.hip.  n = N + 1, nr = 5 N + 8, m = N (mx + mu) + mp.  Weight factors
+// as LbmpcArgs; F_x mx x 4 and F_T mp x 5 column-major; x0 absolute.
+constexpr int NMPC_MAXN = 127;     // n = N + 1 <= 128: two sensitivity columns per lane
+constexpr int NMPC_MAXMX = 32, NMPC_MAXMU = 8;
+struct NmpcArgs {
+    int N, n, nr, m, mx, mu, mp, batch, ntrial, max_iter;
+    double delta, tol_step, tol_stat;
+    const double *Lq, *Lr, *Lp, *Lt, *LAM, *PSI, *xeq, *ueq, *Fx, *hx, *Fu, *hu, *FT, *hT;
+    const double* x0; int64_t sx0;
+    double* z;                          // batch x n iterate (in: start, out: solution)
+    double* d;                          // batch x n QP step
+    double* lam;                        // batch x m QP multipliers
+    double *Jr, *er;                    // batch x nr x n (row-major), batch x nr
+    double *H, *f;                      // batch x n x n (column-major), batch x n
+    double *C, *rhs;                    // batch x m x n (column-major per instance), batch x m: -c
+    double *cost0, *costT, *violT;      // batch, batch x ntrial, batch x ntrial
+    double *stat, *cprev, *nu;          // batch each; nu: the merit function's penalty
+    double *Xout, *cout;                // linearisation only (may be null): rollout, c
+    int *qpflag, *flag, *done, *iters, *ndone;
+};
+bool nmpc_supported(int N, int mx, int mu);
+// gn = 1: rollout with sensitivities at z (Jr, er, C, rhs, cost0); gn = 0: the ntrial trial points
+hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st);
+hipError_t launch_nmpc_update(const NmpcArgs& a, hipStream_t st);
+// closed loop: after the plant step of step t, the step's SQP iteration counts into the log and
+// the warm start (z shifted one stage, last move repeated, theta kept)
+hipError_t launch_nmpc_loop_shift(int batch, int N, int steps, int t, double* z, const int* it,
+                                  int* itlog, hipStream_t st);
+
 // closed-loop simulation (bqp_plant.hip): Moore-Greitzer plant (RK4 step or MATLAB ode23,
 // BQP_PLANT_*) between batched solves
 hipError_t launch_closed_loop_init(int batch, int nx, int steps, const double* xinit,

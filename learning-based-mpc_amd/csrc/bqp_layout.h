@@ -101,6 +101,36 @@ struct Lwork : Arena {
     }
 };
 
+// nwork: the nonlinear MPC SQP's per-instance state (horizon N: n = N + 1 variables, nr = 5 N + 8
+// residual rows, m constraint rows, ntrial line-search trials).  C is the instance's own
+// constraint Jacobian (column-major m x n: 1.3 MB at N = 100 with the 616-row terminal set), so
+// the bytes grow with the batch as no other workspace does; every count is size_t from the
+// start.  ndone follows done directly: one memset zeroes both
+struct Nwork : Arena {
+    size_t n, nr;
+    Region Jr, er, H, f, C, rhs, lam, d, cost0, costT, violT, stat, cprev, nu;
+    Region qpflag, done, ndone;
+    Nwork(size_t B, size_t N, size_t m, size_t ntrial) : n(N + 1), nr(5 * N + 8) {
+        Jr = take<double>(B * nr * n);
+        er = take<double>(B * nr);
+        H = take<double>(B * n * n);
+        f = take<double>(B * n);
+        C = take<double>(B * m * n);
+        rhs = take<double>(B * m);
+        lam = take<double>(B * m);
+        d = take<double>(B * n);
+        cost0 = take<double>(B);
+        costT = take<double>(B * ntrial);
+        violT = take<double>(B * ntrial);
+        stat = take<double>(B);
+        cprev = take<double>(B);
+        nu = take<double>(B);
+        qpflag = take<int>(B);
+        done = take<int>(B);
+        ndone = take<int>(1);
+    }
+};
+
 // dwork: the dense kernel's scratch (work_doubles per instance) and its stats
 struct Dwork : Arena {
     Region scratch, stats;
@@ -156,6 +186,18 @@ struct CworkSqp : Arena {
         ts = take<int>(B);
         nfin = take<int>(1);
         skip(CWORK_SQP_INT_SLACK);
+    }
+};
+
+// cwork of the nonlinear MPC loop: measured deviation state (the plant kernel's, nx = 4), SQP
+// iterate (n), exit flags and iteration counts of the step
+struct CworkNmpc : Arena {
+    Region s, z, flags, iters;
+    CworkNmpc(size_t B, size_t n) {
+        s = take<double>(B * 4);
+        z = take<double>(B * n);
+        flags = take<int>(B);
+        iters = take<int>(B);
     }
 };
 

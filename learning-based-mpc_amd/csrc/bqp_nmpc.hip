@@ -1,0 +1,490 @@
+// bqp_nmpc.hip — nonlinear MPC on the true Moore-Greitzer model on gfx950: the device side of the
+// single-shooting Gauss-Newton SQP that solves the reference's tracking NMPC problem.
+//
+// Reference: examples/DMS_tracking_NMPC_casadi.m:121-126 (the NLP), :225-254 (cost), :256-283
+// (constraint rows), :217-223 / :286-293 (`system`, `dynamic`: one RK4 step).  The algorithm is
+// stated in tests/nmpc_ref.py; the host loop is bqp_nmpc_solve_batched_device (bqp_api.cpp).
+//
+// One SQP iteration = rollout(GN) -> normal equations -> dense QP -> rollout(trials) -> update:
+//   nmpc_rollout_kernel<true>   one wave per instance: the RK4 rollout from the measured state
+//                               with the stage Jacobians A_k, B_k differentiated through the four
+//                               RK stages (analytic Jacobian of `system`), the forward
+//                               sensitivities S_{k+1} = A_k S_k + B_k e_k' (lanes over the columns
+//                               of z, two per lane), the weighted residuals e and the rows of
+//                               their Jacobian Jr (row-major, the layout of the learned-model
+//                               path), the constraint values (rhs = -c) and the instance's own
+//                               constraint Jacobian C (column-major m x n, as the dense kernels
+//                               read A)
+//   nmpc_rollout_kernel<false>  one wave per (instance, trial): cost and violation
+//                               V = sum max(c, 0) at z + 2^-t d, no Jacobians
+//   lbmpc_normal_kernel         (bqp_lbmpc.hip, launched with m = 0) H = 2 Jr'Jr on the fp64
+//                               matrix cores, f = 2 Jr'e
+//   nmpc_update_kernel          one wave per instance: stationarity |f + C'lam| over the
+//                               instance's C, penalty, L1 merit line search, z += alpha d
+//   nmpc_loop_shift_kernel      closed loop: the warm start of the next step
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "bqp_internal.h"
+#include "bqp_wave.h"
+
+namespace bqp {
+
+#define NM_WAVE 64
+#define NM_CPL 2         // z columns per lane: n = N + 1 <= 128
+
+// Moore-Greitzer `system` (as bqp_plant.hip steps it)
+__device__ __forceinline__ void nm_system(const double (&x)[4], double u, double (&f)[4]) {
+    f[0] = -x[1] + 1.0 + 3.0 * (x[0] / 2.0) - (x[0] * x[0] * x[0] / 2.0);
+    f[1] = (x[0] + 1.0 - x[2] * sqrt(x[1]));
+    f[2] = x[3];
+    f[3] = -1000.0 * x[2] - 2.0 * sqrt(500.0) * x[3] + 1000.0 * u;
+}
+
+// R = Jf(y) M + [0 | fu] for a 4 x 5 block M = [d./dx | d./du]: Jf the analytic Jacobian of
+// `system` w.r.t. x (its sparsity written out), fu = d system / du = [0 0 0 1000]'
+__device__ __forceinline__ void nm_jmul(const double (&y)[4], const double (&M)[4][5], double (&R)[4][5]) {
+    const double sq = sqrt(y[1]);
+    const double a00 = 1.5 - 1.5 * y[0] * y[0], a11 = -y[2] / (2.0 * sq), c33 = 2.0 * sqrt(500.0);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        R[0][j] = a00 * M[0][j] - M[1][j];
+        R[1][j] = M[0][j] + a11 * M[1][j] - sq * M[2][j];
+        R[2][j] = M[3][j];
+        R[3][j] = -1000.0 * M[2][j] - c33 * M[3][j];
+    }
+    R[3][4] += 1000.0;
+}
+
+// xn = dynamic(h, x, u); JAC: AB = [dxn/dx | dxn/du], the chain rule through the four stages
+template <bool JAC>
+__device__ __forceinline__ void nm_rk4(double h, const double (&x)[4], double u, double (&xn)[4],
+                                       double (&AB)[4][5]) {
+    double k[4], y[4], ks[4], M[4][5], K[4][5];
+    const double hs[3] = {h / 2.0, h / 2.0, h}, wk[4] = {1.0, 2.0, 2.0, 1.0};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { y[i] = x[i]; ks[i] = 0.0; }
+    if (JAC) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 5; ++j) { M[i][j] = i == j ? 1.0 : 0.0; AB[i][j] = 0.0; }
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        nm_system(y, u, k);
+        if (JAC) {
+            nm_jmul(y, M, K);
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 5; ++j) AB[i][j] += wk[s] * K[i][j];
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ks[i] += wk[s] * k[i];
+        if (s < 3) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) y[i] = x[i] + hs[s] * k[i];
+            if (JAC) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 5; ++j) M[i][j] = (i == j ? 1.0 : 0.0) + hs[s] * K[i][j];
+            }
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xn[i] = x[i] + h / 6.0 * ks[i];
+    if (JAC) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 5; ++j) AB[i][j] = (i == j ? 1.0 : 0.0) + h / 6.0 * AB[i][j];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// rollout: cost and constraint values (all modes); GN: the residual Jacobian Jr and the
+// constraint Jacobian C from the forward sensitivities
+// ------------------------------------------------------------------------------------------
+// the shared constants, copied to LDS once (read from global memory inside the stage loop they
+// would be reloaded after every store: the compiler cannot rule out aliasing)
+constexpr int NO_Q = 0, NO_R = NO_Q + 16, NO_P = NO_R + 1, NO_T = NO_P + 16, NO_L = NO_T + 16,
+              NO_PSI = NO_L + 4, NO_XE = NO_PSI + 1, NO_UE = NO_XE + 4, NO_FX = NO_UE + 1,
+              NO_HX = NO_FX + 4 * NMPC_MAXMX, NO_FU = NO_HX + NMPC_MAXMX, NO_HU = NO_FU + NMPC_MAXMU,
+              NO_END = NO_HU + NMPC_MAXMU;
+
+template <bool GN>
+__global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a) {
+    const int lane = threadIdx.x;
+    const int nt = GN ? 1 : a.ntrial;
+    const int b = blockIdx.x / nt, t = blockIdx.x % nt;
+    if (b >= a.batch || a.done[b]) return;
+    const int N = a.N, n = a.n, m = a.m, mx = a.mx, mu = a.mu, ms = mx + mu, mp = a.mp;
+    __shared__ double zsh[NM_WAVE * NM_CPL];
+    __shared__ double cst[NO_END];
+    __shared__ double SNs[GN ? 4 * NM_WAVE * NM_CPL : 1];   // S_N, row c at SNs[128 c ..]
+    {
+        const double alpha = GN ? 0.0 : ldexp(1.0, -t);
+        const double* z = a.z + (int64_t)b * n;
+        const double* dz = a.d + (int64_t)b * n;
+        for (int j = lane; j < n; j += NM_WAVE) zsh[j] = GN ? z[j] : z[j] + alpha * dz[j];
+    }
+    for (int i = lane; i < NO_END; i += NM_WAVE) {
+        double v = 0.0;
+        if (i < NO_R) v = a.Lq[i - NO_Q];
+        else if (i < NO_P) v = a.Lr[0];
+        else if (i < NO_T) v = a.Lp[i - NO_P];
+        else if (i < NO_L) v = a.Lt[i - NO_T];
+        else if (i < NO_PSI) v = a.LAM[i - NO_L];
+        else if (i < NO_XE) v = a.PSI[0];
+        else if (i < NO_UE) v = a.xeq[i - NO_XE];
+        else if (i < NO_FX) v = a.ueq[0];
+        else if (i < NO_HX) { const int e = i - NO_FX; if (e < 4 * mx) v = a.Fx[e]; }
+        else if (i < NO_FU) { const int e = i - NO_HX; if (e < mx) v = a.hx[e]; }
+        else if (i < NO_HU) { const int e = i - NO_FU; if (e < mu) v = a.Fu[e]; }
+        else { const int e = i - NO_HU; if (e < mu) v = a.hu[e]; }
+        cst[i] = v;
+    }
+    wave_sync();
+    const double th = zsh[N];
+    const double ueq = cst[NO_UE], psi = cst[NO_PSI];
+    double x[4];
+    {
+        const double* x0 = a.x0 + (int64_t)b * a.sx0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = x0[i];
+    }
+    // sensitivities dx_k/dz for the lane's columns j = lane + 64 c
+    double S[NM_CPL][4];
+#pragma unroll
+    for (int c = 0; c < NM_CPL; ++c)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) S[c][i] = 0.0;
+    double* Jr = GN ? a.Jr + (int64_t)b * a.nr * n : nullptr;
+    double* er = GN ? a.er + (int64_t)b * a.nr : nullptr;
+    double* C = GN ? a.C + (int64_t)b * m * n : nullptr;
+    double* rhs = GN ? a.rhs + (int64_t)b * m : nullptr;
+    double* cout = (GN && a.cout) ? a.cout + (int64_t)b * m : nullptr;
+    double* Xout = (GN && a.Xout) ? a.Xout + (int64_t)b * (N + 1) * 4 : nullptr;
+    double J = 0.0, V = 0.0;
+    int row = 0;
+    // weighted residual block L (v - LAMBDA theta) on the deviation v = x - x_eq, L upper
+    // triangular 4 x 4 row-major at cst[oL]; GN: its Jacobian rows from the sensitivities
+    auto xresidual = [&](int oL, const double (&xx)[4]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double e = 0.0;
+#pragma unroll
+            for (int c2 = r; c2 < 4; ++c2) e += cst[oL + 4 * r + c2] * (xx[c2] - cst[NO_XE + c2] - cst[NO_L + c2] * th);
+            J += e * e;
+            if (GN) {
+                if (lane == 0) er[row + r] = e;
+#pragma unroll
+                for (int c = 0; c < NM_CPL; ++c) {
+                    const int j = lane + NM_WAVE * c;
+                    if (j < n) {
+                        double acc = 0.0;
+#pragma unroll
+                        for (int c2 = r; c2 < 4; ++c2)
+                            acc += cst[oL + 4 * r + c2] * (S[c][c2] - (j == N ? cst[NO_L + c2] : 0.0));
+                        Jr[(int64_t)(row + r) * n + j] = acc;
+                    }
+                }
+            }
+        }
+        row += 4;
+    };
+    for (int k = 0; k < N; ++k) {
+        const double vk = zsh[k];
+        if (Xout && lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Xout[4 * k + i] = x[i];
+        }
+        // running cost on (x_k, u_k)
+        xresidual(NO_Q, x);
+        {
+            const double lr = cst[NO_R];
+            const double e = lr * (vk - psi * th);
+            J += e * e;
+            if (GN) {
+                if (lane == 0) er[row] = e;
+#pragma unroll
+                for (int c = 0; c < NM_CPL; ++c) {
+                    const int j = lane + NM_WAVE * c;
+                    if (j < n) Jr[(int64_t)row * n + j] = lr * ((j == k ? 1.0 : 0.0) - (j == N ? psi : 0.0));
+                }
+            }
+            row += 1;
+        }
+        // x_{k+1} = dynamic(delta, x_k, u_k), S_{k+1} = A_k S_k + B_k e_k'
+        double xn[4], AB[4][5];
+        nm_rk4<GN>(a.delta, x, vk + ueq, xn, AB);
+        if (GN) {
+#pragma unroll
+            for (int c = 0; c < NM_CPL; ++c) {
+                const int j = lane + NM_WAVE * c;
+                double sn[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    double v = j == k ? AB[i][4] : 0.0;
+#pragma unroll
+                    for (int c2 = 0; c2 < 4; ++c2) v += AB[i][c2] * S[c][c2];
+                    sn[i] = v;
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) S[c][i] = sn[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = xn[i];
+        // rows of stage k + 1: F_x (x_{k+1} - x_eq) <= h_x, F_u (u_k - u_eq) <= h_u
+        const int r0 = ms * k;
+        for (int i = 0; i < ms; ++i) {
+            double cv;
+            if (i < mx) {
+                cv = -cst[NO_HX + i];
+#pragma unroll
+                for (int c2 = 0; c2 < 4; ++c2) cv += cst[NO_FX + i + mx * c2] * (x[c2] - cst[NO_XE + c2]);
+            } else {
+                cv = cst[NO_FU + i - mx] * vk - cst[NO_HU + i - mx];
+            }
+            V += fmax(cv, 0.0);
+            if (GN) {
+                if (lane == 0) {
+                    rhs[r0 + i] = -cv;
+                    if (cout) cout[r0 + i] = cv;
+                }
+#pragma unroll
+                for (int c = 0; c < NM_CPL; ++c) {
+                    const int j = lane + NM_WAVE * c;
+                    if (j < n) {
+                        double v;
+                        if (i < mx) {
+                            v = 0.0;
+#pragma unroll
+                            for (int c2 = 0; c2 < 4; ++c2) v += cst[NO_FX + i + mx * c2] * S[c][c2];
+                        } else {
+                            v = j == k ? cst[NO_FU + i - mx] : 0.0;
+                        }
+                        C[(int64_t)j * m + r0 + i] = v;
+                    }
+                }
+            }
+        }
+    }
+    if (Xout && lane == 0) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Xout[4 * N + i] = x[i];
+    }
+    // terminal P on x_N, T on LAMBDA theta
+    xresidual(NO_P, x);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        double w = 0.0;
+#pragma unroll
+        for (int c2 = r; c2 < 4; ++c2) w += cst[NO_T + 4 * r + c2] * cst[NO_L + c2];
+        const double e = w * th;
+        J += e * e;
+        if (GN) {
+            if (lane == 0) er[row + r] = e;
+#pragma unroll
+            for (int c = 0; c < NM_CPL; ++c) {
+                const int j = lane + NM_WAVE * c;
+                if (j < n) Jr[(int64_t)(row + r) * n + j] = j == N ? w : 0.0;
+            }
+        }
+    }
+    // terminal rows F_T [x_N - x_eq; theta] <= h_T: lanes over the rows, so that the stores of a
+    // column of C are contiguous across the wave; S_N staged in LDS
+    if (GN) {
+#pragma unroll
+        for (int c = 0; c < NM_CPL; ++c)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) SNs[NM_WAVE * NM_CPL * i + lane + NM_WAVE * c] = S[c][i];
+        wave_sync();
+    }
+    const int rT = ms * N;
+    double Vt = 0.0;
+    for (int r = lane; r < mp; r += NM_WAVE) {
+        double F[5];
+#pragma unroll
+        for (int c2 = 0; c2 < 5; ++c2) F[c2] = a.FT[r + (int64_t)mp * c2];
+        double cv = F[4] * th - a.hT[r];
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) cv += F[c2] * (x[c2] - cst[NO_XE + c2]);
+        Vt += fmax(cv, 0.0);
+        if (GN) {
+            rhs[rT + r] = -cv;
+            if (cout) cout[rT + r] = cv;
+            for (int j = 0; j < n; ++j) {
+                double v = j == N ? F[4] : 0.0;
+#pragma unroll
+                for (int c2 = 0; c2 < 4; ++c2) v += F[c2] * SNs[NM_WAVE * NM_CPL * c2 + j];
+                C[(int64_t)j * m + rT + r] = v;
+            }
+        }
+    }
+    if (!GN) V += wsum(Vt);
+    if (lane == 0) {
+        if (GN) {
+            a.cost0[b] = J;
+        } else {
+            a.costT[(int64_t)b * nt + t] = J;
+            a.violT[(int64_t)b * nt + t] = V;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// convergence test + penalty + L1 merit line search + step (one wave per instance)
+// ------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) nmpc_update_kernel(NmpcArgs a) {
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (b >= a.batch || a.done[b]) return;
+    const int n = a.n, m = a.m;
+    double* z = a.z + (int64_t)b * n;
+    const double* d = a.d + (int64_t)b * n;
+    const double* f = a.f + (int64_t)b * n;
+    const double* lam = a.lam + (int64_t)b * m;
+    const double* rhs = a.rhs + (int64_t)b * m;
+    const double* C = a.C + (int64_t)b * m * n;
+    const int qflag = a.qpflag[b];
+    double st = 0.0, fn = 0.0, dn = 0.0, zn = 0.0, sl = 0.0, viol = -INFINITY, V0 = 0.0, lmax = 0.0;
+    // C'lam by groups of 16 columns: lanes over the rows (coalesced loads, 16 in flight), one
+    // transposed wave sum per group - the pattern of lbmpc_update_kernel over the instance's own C
+    __shared__ double sg[NM_WAVE * NM_CPL];
+    for (int g0 = 0; g0 < n; g0 += 16) {
+        double ac[16];
+#pragma unroll
+        for (int c = 0; c < 16; ++c) ac[c] = 0.0;
+        for (int r = lane; r < m; r += NM_WAVE) {
+            const double lr = lam[r];
+            double av[16];
+#pragma unroll
+            for (int c = 0; c < 16; ++c) av[c] = C[(int64_t)min(g0 + c, n - 1) * m + r];
+#pragma unroll
+            for (int c = 0; c < 16; ++c) ac[c] = fma(av[c], lr, ac[c]);
+        }
+        const double tot = wsum_t(ac, lane);
+        if (lane < 16 && g0 + lane < n) sg[g0 + lane] = tot;
+    }
+    wave_sync();
+    for (int j = lane; j < n; j += NM_WAVE) {
+        const double g = f[j] + sg[j];
+        st = fmax(st, fabs(g));
+        fn = fmax(fn, fabs(f[j]));
+        dn = fmax(dn, fabs(d[j]));
+        zn = fmax(zn, fabs(z[j]));
+        sl += f[j] * d[j];
+    }
+    for (int r = lane; r < m; r += NM_WAVE) {
+        const double cv = -rhs[r];
+        viol = fmax(viol, cv);
+        V0 += fmax(cv, 0.0);
+        lmax = fmax(lmax, lam[r]);
+    }
+    st = wmax(st); fn = wmax(fn); dn = wmax(dn); zn = wmax(zn); sl = wsum(sl);
+    viol = wmax(viol); V0 = wsum(V0); lmax = wmax(lmax);
+    const bool feas0 = viol <= 1e-9;
+    const double J0 = a.cost0[b];
+    int it = a.iters[b];
+    int flag = 0;
+    bool fin = false;
+    // as lbmpc_update_kernel: a QP that stopped on its iteration limit or numerically (-8) still
+    // returns its last interior iterate, and the step is used as is
+    const bool qp_ok = qflag == 1 || ((qflag == 0 || qflag == -8) && isfinite(dn) && isfinite(st));
+    if (qflag == -2 || !qp_ok || !isfinite(J0) || !isfinite(V0)) {
+        flag = (qflag == -2) ? -2 : -8;   // sub-problem infeasible / failed, or a non-finite iterate
+        fin = true;
+    } else if (feas0 && ((qflag == 1 && dn <= a.tol_step * (1.0 + zn) && st <= a.tol_stat * (1.0 + fn)) ||
+                         (it > 0 && dn <= 1e-6 * (1.0 + zn) &&
+                          (qflag != 1 || fabs(a.cprev[b] - J0) <= 1e-12 * (1.0 + fabs(J0)))))) {
+        flag = 1;
+        fin = true;
+    }
+    if (!fin) {
+        // penalty of the L1 merit function phi = J + nu V, kept within the solve
+        const double nu = fmax(a.nu[b], 1.1 * lmax);
+        const double D = sl - nu * V0, phi0 = J0 + nu * V0;
+        int tsel = a.ntrial - 1;
+        for (int t = 0; t < a.ntrial; ++t) {
+            const double al = ldexp(1.0, -t);
+            const double Jt = a.costT[(int64_t)b * a.ntrial + t], Vt = a.violT[(int64_t)b * a.ntrial + t];
+            // a trial whose rollout is not finite (sqrt of x2 <= 0) is rejected
+            if (isfinite(Jt) && isfinite(Vt) && Jt + nu * Vt <= phi0 + 1e-4 * al * D) { tsel = t; break; }
+        }
+        const double Js = a.costT[(int64_t)b * a.ntrial + tsel];
+        if (!isfinite(Js) || !isfinite(a.violT[(int64_t)b * a.ntrial + tsel])) {
+            flag = -8;                    // the accepted iterate would not be finite
+            fin = true;
+        } else {
+            const double al = ldexp(1.0, -tsel);
+            for (int j = lane; j < n; j += NM_WAVE) z[j] += al * d[j];
+            if (lane == 0) { a.cprev[b] = J0; a.nu[b] = nu; }
+            ++it;
+            if (it >= a.max_iter) {
+                flag = 0;
+                fin = true;
+                if (lane == 0) a.cost0[b] = Js;   // the returned z is the stepped iterate
+            }
+        }
+    }
+    if (lane == 0) {
+        a.iters[b] = it;
+        a.stat[b] = st;
+        if (fin) {
+            a.flag[b] = flag;
+            a.done[b] = 1;
+            atomicAdd(a.ndone, 1);
+        }
+    }
+}
+
+// closed loop, after the plant step of step t: the step's iteration count into the log, then the
+// warm start of step t + 1: z shifted one stage, the last move repeated, theta kept
+__global__ void __launch_bounds__(64) nmpc_loop_shift_kernel(int batch, int N, int steps, int t, double* z,
+                                                             const int* it, int* itlog) {
+    __shared__ double zs[NM_WAVE * NM_CPL];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= batch) return;
+    double* zb = z + (int64_t)b * (N + 1);
+    for (int j = lane; j < N; j += NM_WAVE) zs[j] = zb[min(j + 1, N - 1)];
+    wave_sync();
+    for (int j = lane; j < N; j += NM_WAVE) zb[j] = zs[j];
+    if (lane == 0 && itlog) itlog[(int64_t)b * steps + t] = it[b];
+}
+
+// ------------------------------------------------------------------------------------------
+// launch helpers
+// ------------------------------------------------------------------------------------------
+bool nmpc_supported(int N, int mx, int mu) {
+    return N >= 1 && N <= NMPC_MAXN && N + 1 <= NM_WAVE * NM_CPL && mx >= 0 && mx <= NMPC_MAXMX &&
+           mu >= 0 && mu <= NMPC_MAXMU;
+}
+
+hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st) {
+    if (!nmpc_supported(a.N, a.mx, a.mu) || a.n != a.N + 1 || a.nr != 5 * a.N + 8 ||
+        a.m != a.N * (a.mx + a.mu) + a.mp)
+        return hipErrorInvalidValue;
+    if (gn) hipLaunchKernelGGL(nmpc_rollout_kernel<true>, dim3(a.batch), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(nmpc_rollout_kernel<false>, dim3(a.batch * a.ntrial), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_update(const NmpcArgs& a, hipStream_t st) {
+    if (a.n > NM_WAVE * NM_CPL) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_update_kernel, dim3(a.batch), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_loop_shift(int batch, int N, int steps, int t, double* z, const int* it,
+                                  int* itlog, hipStream_t st) {
+    if (N < 1 || N > NMPC_MAXN) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_loop_shift_kernel, dim3(batch), dim3(64), 0, st, batch, N, steps, t, z, it, itlog);
+    return hipGetLastError();
+}
+
+}  // namespace bqp
