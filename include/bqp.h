@@ -479,12 +479,21 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
                                   double* lam, double* cost, int* exitflag, int* iterations,
                                   void* stream);
 
-/* Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states, step
- * synchronous: the solve at the measured states, the RK4 plant with u_0 (cl->plant must be
- * BQP_PLANT_MG_RK4, cl->delta the plant's step; data->x0 is ignored), then the warm start - z
- * shifted one stage with the last move repeated and theta kept.  steps = 0 is allowed and returns
- * X = x_init.  X (batch*(steps+1)*4), U (batch*steps) absolute; exitflag and iterations
- * (batch*steps, may be NULL) per solve.  The loop's time goes to bqp_last_kernel_ms. */
+/* Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states: per step the
+ * solve at the measured state, the RK4 plant with u_0 (cl->plant must be BQP_PLANT_MG_RK4,
+ * cl->delta the plant's step; data->x0 is ignored), then the warm start - z shifted one stage
+ * with the last move repeated and theta kept.  Every instance advances at its own step: one round
+ * is one SQP iteration of every instance that has steps to go (rollout, normal equations, dense
+ * sub-problem, trial rollouts, update) and one advance launch that moves the instances whose SQP
+ * stopped in this round to their next step, so the loop takes as many rounds as its slowest
+ * instance needs over all steps, not the sum over the steps of the slowest instance of each.
+ * With the environment variable BQP_NMPC_SYNC set (read at each call) the loop is step
+ * synchronous instead - every step's SQP runs until the whole batch has stopped; per instance both
+ * forms do the same operations in the same order and return the same bits.  steps = 0 is allowed
+ * and returns X = x_init.  X (batch*(steps+1)*4), U (batch*steps) absolute; exitflag and iterations
+ * (batch*steps, may be NULL) per solve.  The loop's time goes to bqp_last_kernel_ms (6 launches
+ * per round), its rounds to bqp_last_loop_rounds.  The _device variant synchronises its stream
+ * while it polls for the instances that have finished. */
 int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
                          const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,
                          double* X, double* U, int* exitflag, int* iterations);
@@ -496,6 +505,11 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
 /* Timing of the most recent solve on this handle: kernel time measured with hipEvents on the
  * launch stream (ms), and the number of kernel launches it covered. */
 int bqp_last_kernel_ms(bqp_handle h, double* ms, int* launches);
+
+/* SQP rounds that the most recent bqp_closed_loop_nmpc[_device] on this handle launched, in either
+ * of its modes; a round is one launch of rollout, normal equations, dense sub-problem, trial
+ * rollouts and update.  BQP_E_ARG before any such loop has run on the handle. */
+int bqp_last_loop_rounds(bqp_handle h, int* rounds);
 
 /* Diagnostic: per instance of the most recent mixed-precision structured solve on this handle
  * (bqp_options.precision = 2, N + 1 > 64), the fp32 phase's exit flag (1 / 0: continued in fp64

@@ -93,7 +93,8 @@ EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'b
            'bqp_closed_loop_lbmpc_device', 'bqp_closed_loop_sqp', 'bqp_closed_loop_sqp_device',
            'bqp_closed_loop_track', 'bqp_closed_loop_track_device', 'bqp_debug_mixed_flags',
            'bqp_nmpc_linearize', 'bqp_nmpc_linearize_device', 'bqp_nmpc_solve_batched',
-           'bqp_nmpc_solve_batched_device', 'bqp_closed_loop_nmpc', 'bqp_closed_loop_nmpc_device']
+           'bqp_nmpc_solve_batched_device', 'bqp_closed_loop_nmpc', 'bqp_closed_loop_nmpc_device',
+           'bqp_last_loop_rounds']
 
 _lib = None
 
@@ -176,6 +177,7 @@ def load():
                                          C.POINTER(NmpcData), C.POINTER(Options), C.c_void_p, _PD,
                                          _PD, _PD, _PI, _PI]
     lib.bqp_closed_loop_nmpc_device.argtypes = lib.bqp_closed_loop_nmpc.argtypes + [C.c_void_p]
+    lib.bqp_last_loop_rounds.argtypes = [C.c_void_p, _PI]
     _lib = lib
     return lib
 
@@ -230,6 +232,12 @@ class Handle:
         n = C.c_int(0)
         check(self._lib.bqp_last_kernel_ms(self._h, C.byref(ms), C.byref(n)), 'bqp_last_kernel_ms')
         return ms.value, n.value
+
+    def loop_rounds(self):
+        """SQP rounds launched by the last bqp_closed_loop_nmpc on this handle (bqp_last_loop_rounds)"""
+        n = C.c_int(0)
+        check(self._lib.bqp_last_loop_rounds(self._h, C.byref(n)), 'bqp_last_loop_rounds')
+        return n.value
 
     def mixed_flags(self, batch):
         """per instance of the last mixed-precision solve on this handle: the fp32 phase's exit

@@ -117,9 +117,11 @@ class NMPC:
 
 def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, polish=0):
     """Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states x_init
-    (batch, 4), absolute: per step the batched solve at the measured states, the RK4 plant with
-    u_0, and the warm start (z shifted one stage, last move repeated, theta kept).  Returns
-    X (batch, steps + 1, 4), U (batch, steps), exitflag and iterations (batch, steps), ms."""
+    (batch, 4), absolute: per step the solve at the measured state, the RK4 plant with u_0, and
+    the warm start (z shifted one stage, last move repeated, theta kept).  Every instance advances
+    at its own step (with BQP_NMPC_SYNC set in the environment: the whole batch step by step, same
+    results).  Returns X (batch, steps + 1, 4), U (batch, steps), exitflag and iterations
+    (batch, steps), kernel_ms, launches and rounds, the SQP rounds the loop launched."""
     lib = _lib.load()
     h = handle or _default_handle()
     xi = _f64(np.atleast_2d(x_init))
@@ -133,4 +135,5 @@ def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, p
                                   _lib.ptr(xi), _lib.ptr(X), _lib.ptr(U), _lib.iptr(fl), _lib.iptr(it))
     _lib.check(rc, 'bqp_closed_loop_nmpc')
     ms, launches = h.kernel_ms()
-    return OcpResult(X=X, U=U, exitflag=fl, iterations=it, kernel_ms=ms, launches=launches)
+    return OcpResult(X=X, U=U, exitflag=fl, iterations=it, kernel_ms=ms, launches=launches,
+                     rounds=h.loop_rounds())

@@ -57,6 +57,8 @@ struct bqp_handle_s {
     int* mixed_flags = nullptr;   // the last mixed-mode solve's fp32-phase flags
     int* mixed_cont = nullptr;    // and its continuation's exit flags (bqp_debug_mixed_flags)
     int mixed_batch = 0;
+    int nmpc_rounds = 0;          // SQP rounds of the last bqp_nmpc_solve_batched_device
+    int loop_rounds = -1;         // and of the last bqp_closed_loop_nmpc_device (-1: none yet)
 };
 
 namespace {
@@ -260,6 +262,12 @@ int bqp_last_kernel_ms(bqp_handle h, double* ms, int* launches) {
     float f = 0.f;
     HIP_TRY(hipEventElapsedTime(&f, h->ev0, h->ev1));
     *ms = (double)f;
+    return BQP_OK;
+}
+
+int bqp_last_loop_rounds(bqp_handle h, int* rounds) {
+    if (!h || !rounds || h->loop_rounds < 0) return BQP_E_ARG;
+    *rounds = h->loop_rounds;
     return BQP_OK;
 }
 
@@ -1497,6 +1505,7 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
     HIP_TRY(hipMemsetAsync(a.flag, 0, sizeof(int) * B, st));
     HIP_TRY(hipEventRecord(h->ev0, st));
     int launches = 0;
+    h->nmpc_rounds = 0;
     // BQP_LB_TRACE diagnostics on stderr, as the learned-model solve's: 1 the sub-problems' exit
     // flags per iteration (and whether their steps are finite), 2 per-launch event times instead.
     // Both wait for the stream at each iteration; neither launches a kernel.
@@ -1546,6 +1555,7 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
         HIP_TRY(bqp::launch_nmpc_update(a, st));
         BQP_TRY(mark(5));
         launches += 5;
+        ++h->nmpc_rounds;
         if (trace) {
             HIP_TRY(hipEventSynchronize(ev[5].e));
             float ms[5];
@@ -1613,7 +1623,10 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     hipStream_t st = (hipStream_t)stream;
     const int N = d->N, n = N + 1, S = cl->steps;
     const size_t B = batch;
-    const layout::CworkNmpc CL(batch, n);
+    // BQP_NMPC_SYNC selects the step-synchronous loop below (the asynchronous loop's bitwise
+    // reference in tests/test_gpu_nmpc_async.py, and the path BQP_LB_TRACE reports on)
+    const bool sync_loop = getenv("BQP_NMPC_SYNC") != nullptr;
+    const layout::CworkNmpc CL(batch, n, !sync_loop);
     HIP_TRY(h->cwork.reserve(CL.bytes));
     double* s = layout::at<double>(h->cwork.p, CL.s);
     double* z = layout::at<double>(h->cwork.p, CL.z);
@@ -1624,13 +1637,66 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     EventGuard e0;
     HIP_TRY(hipEventCreate(&e0.e));
     HIP_TRY(hipEventRecord(e0.e, st));
-    int launches = 0;
+    int launches = 0, rounds = 0;
     bqp_nmpc_data Dl = *D;
-    Dl.sx0 = (int64_t)(S + 1) * 4;
-    for (int t = 0; t < S; ++t) {
+    if (!sync_loop && S > 0) {
+        // asynchronous: every instance runs at its own closed-loop step.  Each round is one SQP
+        // iteration of every unfinished instance, then nmpc_loop_advance_kernel moves the instances
+        // whose SQP has stopped to their next step (logs, plant, warm start, measured state, the
+        // per-solve state reset).  The step-synchronous form below runs every step's SQP launches
+        // until the batch's slowest instance has stopped while the others idle; per instance the
+        // two forms do the same operations in the same order.
+        int* ts = layout::at<int>(h->cwork.p, CL.ts);
+        int* nfin = layout::at<int>(h->cwork.p, CL.nfin);
+        double* x0 = layout::at<double>(h->cwork.p, CL.x0);
+        HIP_TRY(hipMemsetAsync(ts, 0, sizeof(int) * (B + 1), st));   // ts[], nfin
+        HIP_TRY(hipMemcpyAsync(x0, x_init, sizeof(double) * B * 4, hipMemcpyDeviceToDevice, st));
+        Dl.x0 = x0;                      // the measured states, absolute: the bits of X[b, ts[b]]
+        Dl.sx0 = 4;
+        bqp_options o;
+        resolve(opt, &o);
+        bqp::NmpcArgs a;
+        bqp::LbmpcArgs ne;
+        bqp::DenseKernelArgs q;
+        HIP_TRY(nmpc_setup(h, d, batch, &Dl, o, nullptr, nullptr, nullptr, st, a, ne, &q));
+        a.z = z; ne.z = z; a.flag = fl; a.iters = it;
+        HIP_TRY(hipMemsetAsync(it, 0, sizeof(int) * B, st));
+        HIP_TRY(hipMemsetAsync(fl, 0, sizeof(int) * B, st));
+        // sub-problem polish only where the caller asks for it (bqp_nmpc_solve_batched_device), per
+        // instance from its own SQP iteration count: mode 2 from LB_POLISH_STALL on
+        q.polish = o.polish > 0 ? sub_polish(o.polish, false) : 0;
+        q.pol_it = o.polish > 0 ? a.iters : nullptr;
+        q.pol_stall = LB_POLISH_STALL;
+        bqp::NmpcAdvanceArgs v;
+        memset(&v, 0, sizeof(v));
+        v.batch = batch; v.N = N; v.steps = S; v.plant = cl->plant; v.delta = cl->delta;
+        v.xeq = cl->x_eq; v.ueq = cl->u_eq;
+        v.s = s; v.z = z; v.x0 = x0; v.X = X; v.U = U; v.nu = a.nu;
+        v.done = a.done; v.iters = it; v.flag = fl; v.ts = ts; v.nfin = nfin;
+        v.flags = exitflag; v.itlog = iterations;
+        // an instance stops within max_iter rounds of its step's first: the bound is never reached
+        const int64_t max_rounds = (int64_t)S * o.max_iter;
+        for (int64_t r = 0; r < max_rounds; ++r) {
+            HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st));
+            HIP_TRY(bqp::launch_lbmpc_normal(ne, st));
+            HIP_TRY(bqp::launch_dense(q, st));
+            HIP_TRY(bqp::launch_nmpc_rollout(a, 0, st));
+            HIP_TRY(bqp::launch_nmpc_update(a, st));
+            HIP_TRY(bqp::launch_nmpc_loop_advance(v, st));
+            launches += 6;
+            ++rounds;
+            int nf = 0;
+            HIP_TRY(hipMemcpyAsync(&nf, nfin, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (nf >= batch) break;
+        }
+    }
+    for (int t = 0; t < (sync_loop ? S : 0); ++t) {
         Dl.x0 = X + (int64_t)t * 4;      // the measured states X[:, t], absolute
+        Dl.sx0 = (int64_t)(S + 1) * 4;
         BQP_TRY(bqp_nmpc_solve_batched_device(h, d, batch, &Dl, opt, z, nullptr, nullptr, fl, it, stream));
         launches += h->launches;
+        rounds += h->nmpc_rounds;
         // the plant reads u_0 - u_eq = z[b, 0] (stride n)
         HIP_TRY(bqp::launch_mg_plant(cl->plant, batch, n, S, t, cl->delta, z, fl, cl->x_eq, cl->u_eq,
                                      s, X, U, exitflag, st));
@@ -1642,6 +1708,7 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     std::swap(h->ev0, e0.e);   // the guard destroys the previous start event
     h->timed = true;
     h->launches = launches;
+    h->loop_rounds = rounds;
     return BQP_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bqp_nmpc_advance.h"
 #include "bqp_track.h"
 
 namespace bqp {
@@ -184,6 +185,9 @@ hipError_t launch_nmpc_update(const NmpcArgs& a, hipStream_t st);
 // the warm start (z shifted one stage, last move repeated, theta kept)
 hipError_t launch_nmpc_loop_shift(int batch, int N, int steps, int t, double* z, const int* it,
                                   int* itlog, hipStream_t st);
+// asynchronous closed loop (NmpcAdvanceArgs: bqp_nmpc_advance.h): after an SQP round, every instance
+// whose SQP has stopped logs its step, steps the plant and sets up its next solve
+hipError_t launch_nmpc_loop_advance(const NmpcAdvanceArgs& a, hipStream_t st);
 
 // closed-loop simulation (bqp_plant.hip): Moore-Greitzer plant (RK4 step or MATLAB ode23,
 // BQP_PLANT_*) between batched solves

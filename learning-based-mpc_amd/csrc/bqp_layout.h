@@ -190,14 +190,22 @@ struct CworkSqp : Arena {
 };
 
 // cwork of the nonlinear MPC loop: measured deviation state (the plant kernel's, nx = 4), SQP
-// iterate (n), exit flags and iteration counts of the step
+// iterate (n), exit flags and iteration counts of the step.  The asynchronous loop (own_step)
+// adds the instances' step counters, the count of finished instances - nfin follows ts directly:
+// one memset zeroes both - and the measured state in absolute coordinates (4 per instance, the
+// solve's x0); the step-synchronous loop's layout is unchanged by it
 struct CworkNmpc : Arena {
-    Region s, z, flags, iters;
-    CworkNmpc(size_t B, size_t n) {
+    Region s, z, flags, iters, ts, nfin, x0;
+    CworkNmpc(size_t B, size_t n, bool own_step = false) {
         s = take<double>(B * 4);
         z = take<double>(B * n);
         flags = take<int>(B);
         iters = take<int>(B);
+        if (own_step) {
+            ts = take<int>(B);
+            nfin = take<int>(1);
+            x0 = take<double>(B * 4);
+        }
     }
 };
 

@@ -21,12 +21,15 @@
 //                               matrix cores, f = 2 Jr'e
 //   nmpc_update_kernel          one wave per instance: stationarity |f + C'lam| over the
 //                               instance's C, penalty, L1 merit line search, z += alpha d
-//   nmpc_loop_shift_kernel      closed loop: the warm start of the next step
+//   nmpc_loop_shift_kernel      step-synchronous closed loop: the warm start of the next step
+//   nmpc_loop_advance_kernel    asynchronous closed loop, after every iteration: the instances
+//                               whose SQP has stopped move to their next closed-loop step
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
 
 #include "bqp_internal.h"
+#include "bqp_mg.h"
 #include "bqp_wave.h"
 
 namespace bqp {
@@ -457,6 +460,41 @@ __global__ void __launch_bounds__(64) nmpc_loop_shift_kernel(int batch, int N, i
     if (lane == 0 && itlog) itlog[(int64_t)b * steps + t] = it[b];
 }
 
+// asynchronous closed loop (bqp_closed_loop_nmpc_device): every instance runs at its own
+// closed-loop step ts[b].  Launched after every SQP round, one wave per instance: an instance whose
+// SQP stopped in this round and that has steps to go logs the step, steps the plant with u_0
+// (mg_plant_kernel's arithmetic on the shared mg_plant_step: bqp_mg.h says why not mg_rk4 alone)
+// and, unless that was its last step, takes the warm start (nmpc_loop_shift_kernel's) and the
+// measured state for its next solve with the
+// per-solve state reset - per instance the operations of the step-synchronous loop in its order.
+// Every other wave leaves at once.  The indices are bqp_nmpc_advance.h's (checked on the host).
+__global__ void __launch_bounds__(64) nmpc_loop_advance_kernel(NmpcAdvanceArgs a) {
+    __shared__ double zs[NM_WAVE * NM_CPL];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= a.batch || !nmpc_advance_due(a, b)) return;   // uniform per wave
+    const int t = a.ts[b], N = a.N;
+    const bool more = t + 1 < a.steps;
+    double* zb = a.z + (int64_t)b * (N + 1);
+    // every read of z (u_0, the shift's sources) and of the counters before the wave sync, every
+    // write after it
+    const double u0 = zb[0];
+    if (more)
+        for (int j = lane; j < N; j += NM_WAVE) nmpc_shift_stage(zb, N, j, zs);
+    wave_sync();
+    if (more)
+        for (int j = lane; j < N; j += NM_WAVE) nmpc_shift_store(zb, j, zs);
+    if (lane == 0) {
+        nmpc_advance_log(a, b, t);
+        double x[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = a.s[(int64_t)b * 4 + i] + a.xeq[i];
+        const double u = u0 + a.ueq[0];
+        mg_plant_step(a.plant, a.delta, x, u);
+        nmpc_advance_record(a, b, t, x, u);
+        nmpc_advance_next(a, b, t);
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // launch helpers
 // ------------------------------------------------------------------------------------------
@@ -484,6 +522,14 @@ hipError_t launch_nmpc_loop_shift(int batch, int N, int steps, int t, double* z,
                                   int* itlog, hipStream_t st) {
     if (N < 1 || N > NMPC_MAXN) return hipErrorInvalidValue;
     hipLaunchKernelGGL(nmpc_loop_shift_kernel, dim3(batch), dim3(64), 0, st, batch, N, steps, t, z, it, itlog);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_loop_advance(const NmpcAdvanceArgs& a, hipStream_t st) {
+    // the shift stages N <= 128 doubles in LDS
+    if (a.batch < 1 || a.N < 1 || a.N > NMPC_MAXN || a.N > NM_WAVE * NM_CPL || a.steps < 1)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_loop_advance_kernel, dim3(a.batch), dim3(64), 0, st, a);
     return hipGetLastError();
 }
 

@@ -6,6 +6,8 @@ Warmed up; timed with the library's device events around work that ends in a syn
 (bqp_last_kernel_ms).  Prints one JSON line.
 
   --batch B --steps S --warmup W   sizes (defaults 256, 100, 1)
+  --sync     the closed loop step-synchronous (BQP_NMPC_SYNC set for the loop run alone; the
+             default is the asynchronous loop); `loop_rounds` is printed in both modes
   --split    also the split of an SQP iteration over linearise / normal equations / dense /
              trials / update: a child process runs the cold solves with BQP_LB_TRACE=2 and its
              per-iteration lines are summed here
@@ -56,6 +58,7 @@ def main():
     ap.add_argument('--batch', type=int, default=256)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--sync', action='store_true')
     ap.add_argument('--split', action='store_true')
     ap.add_argument('--child', action='store_true')
     a = ap.parse_args()
@@ -92,10 +95,20 @@ def main():
         xnl = np.load(os.path.join(ROOT, 'tests', 'golden', 'nmpc_DSS_tNMPC.npz'))['xnl']
         xi = np.tile(xnl[:, 0], (a.batch, 1))
         xi[1:, :2] += rng.uniform(-0.02, 0.02, (a.batch - 1, 2))
-        if a.warmup:
-            bqp.closed_loop_nmpc(g, xi, 2, handle=h)
-        r = bqp.closed_loop_nmpc(g, xi, a.steps, handle=h)
-        out.update(loop_steps=a.steps, loop_ms=r.kernel_ms,
+        assert 'BQP_NMPC_SYNC' not in os.environ, 'select the loop with --sync'
+        if a.sync:
+            os.environ['BQP_NMPC_SYNC'] = '1'
+        try:
+            if a.warmup:
+                bqp.closed_loop_nmpc(g, xi, 2, handle=h)
+            r = bqp.closed_loop_nmpc(g, xi, a.steps, handle=h)
+        finally:
+            os.environ.pop('BQP_NMPC_SYNC', None)
+        out.update(loop_mode='sync' if a.sync else 'async', loop_steps=a.steps, loop_ms=r.kernel_ms,
+                   loop_rounds=r.rounds,
+                   loop_rounds_from_logs=int((r.iterations + (r.exitflag != 0)).sum(axis=1).max()),
+                   loop_rounds_stepwise=int((r.iterations + (r.exitflag != 0)).max(axis=0).sum()),
+                   loop_flags={str(int(k)): int((r.exitflag == k).sum()) for k in np.unique(r.exitflag)},
                    instance_steps_per_s=a.batch * a.steps / r.kernel_ms * 1e3,
                    loop_iterations_mean=float(r.iterations.mean()),
                    loop_iterations_max=int(r.iterations.max()),
