@@ -97,6 +97,7 @@ typedef struct {
  * Structured OCP (form F1/F2/F4/F5 after the host shim's change of variables):
  *
  *   x_{k+1} = A x_k + B u_k + c              k = 0..N-1,   x_0 = x0 (fixed)
+ *             (A_k x_k + B_k u_k + c_k with bqp_ocp_dims.stage_models = 1)
  *   theta  in R^np  (global steady-state parameter, free)
  *   min  sum_{k=0}^{N} 0.5 v_k' W_k v_k + w_k' v_k,  v_k = [x_k; u_k; theta]  (nv = nx+nu+np;
  *        for k = N the u block of W_N / w_N is ignored)
@@ -111,12 +112,26 @@ typedef struct {
     int nx, nu, np, N;
     int n_poly;      /* rows of the polytope block (>= 0) */
     int poly_stage;  /* stage the polytope acts on, 0..N */
+    int stage_models; /* 0 (a zero-initialised caller): A, B, c are one model for the whole horizon.
+                         1: per-stage models (linear time-varying),
+                             x_{k+1} = A_k x_k + B_k u_k + c_k,
+                         A holds N blocks nx*nx (stage k's block at A + k*nx*nx maps x_k to
+                         x_{k+1}), B N blocks nx*nu, c N blocks nx (NULL = 0).  Strides sA / sB /
+                         sc: 0 = one schedule shared by the batch, otherwise >= N*nx*nx (N*nx*nu,
+                         N*nx); a smaller non-zero stride is BQP_E_ARG.  fp64 only: with
+                         bqp_options.precision 1 or 2 the call returns BQP_E_UNSUPPORTED.  The
+                         active-set polish's repair launch carries the per-stage models (it runs
+                         on the same Riccati routines as the solve, each reading stage k's A_k,
+                         B_k, c_k), so bqp_options.polish means what it means with one model.
+                         bqp_ocp_duals.pi is written against the
+                         stage's own A_k, B_k.  bqp_solve_ocp_batched[_device] only: the closed-loop
+                         routines return BQP_E_UNSUPPORTED.  Any other value is BQP_E_ARG */
 } bqp_ocp_dims;
 
 typedef struct {
-    const double* A;    /* nx*nx                                  stride sA  */
-    const double* B;    /* nx*nu                                  stride sB  */
-    const double* c;    /* nx, NULL = 0                           stride sc  */
+    const double* A;    /* nx*nx      (stage_models = 1: N blocks) stride sA  */
+    const double* B;    /* nx*nu      (stage_models = 1: N blocks) stride sB  */
+    const double* c;    /* nx, NULL = 0 (stage_models = 1: N blocks) stride sc  */
     const double* W;    /* (N+1) blocks nv*nv                     stride sW  */
     const double* w;    /* (N+1)*nv, NULL = 0                     stride sw  */
     const double* xlb;  /* (N+1)*nx, NULL = -inf (stage 0 unused) stride sxb */
@@ -127,6 +142,11 @@ typedef struct {
     const double* hp;   /* n_poly                                 stride shp */
     const double* x0;   /* nx                                     stride sx0 */
     int64_t sA, sB, sc, sW, sw, sxb, sub, sFp, shp, sx0;
+    const int* skip;    /* batch ints, NULL (a zero-initialised caller) = solve every instance;
+                           with bqp_ocp_dims.stage_models = 1 an instance with skip[i] != 0 is
+                           not solved and none of its outputs is written (finished instances
+                           of an outer iteration).  Non-NULL with stage_models = 0 is
+                           BQP_E_UNSUPPORTED */
 } bqp_ocp_data;
 
 /* Optional multiplier outputs of the structured solve (NULL members are skipped).  Sign
@@ -517,6 +537,9 @@ int bqp_last_loop_rounds(bqp_handle h, int* rounds);
  * not converge and the retry launch solved the instance again from the fp64 initial point
  * (tests/test_gpu_mixed.py).  batch must equal that solve's. */
 int bqp_debug_mixed_flags(bqp_handle h, int batch, int* flags);
+/* Diagnostic: instances per workgroup the last structured solve on this handle was launched with
+ * (the most that fit the 160 KB of LDS, at most 4, 2 at N + 1 > 64); BQP_E_ARG before any solve. */
+int bqp_debug_ocp_wpb(bqp_handle h, int* wpb);
 
 #ifdef __cplusplus
 }

@@ -33,12 +33,13 @@ class Output(C.Structure):
 
 class OcpDims(C.Structure):
     _fields_ = [('nx', C.c_int), ('nu', C.c_int), ('np', C.c_int), ('N', C.c_int),
-                ('n_poly', C.c_int), ('poly_stage', C.c_int)]
+                ('n_poly', C.c_int), ('poly_stage', C.c_int), ('stage_models', C.c_int)]
 
 
 class OcpData(C.Structure):
     _fields_ = [(n, _PD) for n in ('A', 'B', 'c', 'W', 'w', 'xlb', 'xub', 'ulb', 'uub', 'Fp', 'hp', 'x0')] + \
-               [(n, C.c_int64) for n in ('sA', 'sB', 'sc', 'sW', 'sw', 'sxb', 'sub', 'sFp', 'shp', 'sx0')]
+               [(n, C.c_int64) for n in ('sA', 'sB', 'sc', 'sW', 'sw', 'sxb', 'sub', 'sFp', 'shp', 'sx0')] + \
+               [('skip', _PI)]
 
 
 class OcpDuals(C.Structure):
@@ -92,6 +93,7 @@ EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'b
            'bqp_closed_loop_ocp', 'bqp_closed_loop_ocp_device', 'bqp_closed_loop_lbmpc',
            'bqp_closed_loop_lbmpc_device', 'bqp_closed_loop_sqp', 'bqp_closed_loop_sqp_device',
            'bqp_closed_loop_track', 'bqp_closed_loop_track_device', 'bqp_debug_mixed_flags',
+           'bqp_debug_ocp_wpb',
            'bqp_nmpc_linearize', 'bqp_nmpc_linearize_device', 'bqp_nmpc_solve_batched',
            'bqp_nmpc_solve_batched_device', 'bqp_closed_loop_nmpc', 'bqp_closed_loop_nmpc_device',
            'bqp_last_loop_rounds']
@@ -232,6 +234,13 @@ class Handle:
         n = C.c_int(0)
         check(self._lib.bqp_last_kernel_ms(self._h, C.byref(ms), C.byref(n)), 'bqp_last_kernel_ms')
         return ms.value, n.value
+
+    def ocp_wpb(self):
+        """instances per workgroup of the last structured solve on this handle (bqp_debug_ocp_wpb)"""
+        n = C.c_int(0)
+        self._lib.bqp_debug_ocp_wpb.argtypes = [C.c_void_p, _PI]
+        check(self._lib.bqp_debug_ocp_wpb(self._h, C.byref(n)), 'bqp_debug_ocp_wpb')
+        return n.value
 
     def loop_rounds(self):
         """SQP rounds launched by the last bqp_closed_loop_nmpc on this handle (bqp_last_loop_rounds)"""

@@ -59,11 +59,40 @@ class OcpResult(dict):
     __getattr__ = dict.__getitem__
 
 
-def pack(prob, x0, w=None, hp=None, A=None, B=None, Fp=None, W=None):
+def _stage_models(prob, batch, A, B, c, stage_models):
+    """True when A / B / c are per-stage schedules: (N, nx, nx) / (N, nx, nu) / (N, nx) shared by
+    the batch, or (batch, N, ...) per instance - beside (nx, nx) and (batch, nx, nx) for one model
+    per horizon.  A three-dimensional A (two-dimensional c) is a schedule when its first axis is
+    N and not batch.  With batch == N the two readings coincide: the array is then one model per
+    instance, as it was before schedules existed, and a schedule shared by the batch is asked
+    for with stage_models=True."""
+    if stage_models is not None:
+        return bool(stage_models)
+    sched = None
+    for a, base in ((A, 2), (B, 2), (c, 1)):
+        if a is None:
+            continue
+        nd = np.ndim(a)
+        if nd == base + 2:
+            return True
+        if nd == base + 1:
+            n0 = np.shape(a)[0]
+            this = n0 == prob.N and n0 != batch
+            if sched is not None and sched != this:
+                raise ValueError('A, B and c must all be schedules or all single models')
+            sched = this
+    return bool(sched)
+
+
+def pack(prob, x0, w=None, hp=None, A=None, B=None, Fp=None, W=None, c=None, stage_models=None,
+         skip=None):
     """Builds (dims, data, keepalive) for a batch.  x0: (batch, nx); per-instance overrides
-    w (batch, N+1, nv), hp (batch, mp), A (batch, nx, nx), B (batch, nx, nu) and the polytope
-    Fp (batch, mp, nv) (same row count and stage as prob's) and the stage costs W (batch, N+1, nv,
-    nv)."""
+    w (batch, N+1, nv), hp (batch, mp), A (batch, nx, nx), B (batch, nx, nu), c (batch, nx) and the
+    polytope Fp (batch, mp, nv) (same row count and stage as prob's) and the stage costs W (batch,
+    N+1, nv, nv).  Per-stage models (bqp_ocp_dims.stage_models = 1): A (N, nx, nx), B (N, nx, nu),
+    c (N, nx) as one schedule for the batch, or (batch, N, ...) per instance; what is not given is
+    prob's model repeated over the stages.  skip (batch,) ints: with per-stage models, instances
+    that are not solved."""
     x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
     batch = x0.shape[0]
     keep = [x0]
@@ -74,37 +103,66 @@ def pack(prob, x0, w=None, hp=None, A=None, B=None, Fp=None, W=None):
         return a
 
     nx, nu, nv, N, mp = prob.nx, prob.nu, prob.nv, prob.N, prob.mp
-    Aa = arr(_cm(prob.A if A is None else A))
-    Ba = arr(_cm(prob.B if B is None else B))
+    stg = _stage_models(prob, batch, A, B, c, stage_models)
+    if stg:
+        def sched(a, base, shape):
+            # (N, *shape) shared or (batch, N, *shape) per instance; a single model is repeated
+            a = np.asarray(base if a is None else a, float)
+            if a.ndim == len(shape):
+                a = np.broadcast_to(a, (N,) + shape)
+            if a.shape not in ((N,) + shape, (batch, N) + shape):
+                raise ValueError('per-stage model of shape %r, expected %r or %r'
+                                 % (a.shape, (N,) + shape, (batch, N) + shape))
+            return a, (0 if a.ndim == len(shape) + 1 else N * int(np.prod(shape)))
+        Am, sA = sched(A, prob.A, (nx, nx))
+        Bm, sB = sched(B, prob.B, (nx, nu))
+        cm, sc = sched(c, prob.c, (nx,))
+        Aa, Ba, ca = arr(_cm(Am)), arr(_cm(Bm)), arr(cm)
+    else:
+        Aa = arr(_cm(prob.A if A is None else A))
+        Ba = arr(_cm(prob.B if B is None else B))
+        ca = arr(prob.c if c is None else c)
+        sA = 0 if A is None else nx * nx
+        sB = 0 if B is None else nx * nu
+        sc = 0 if c is None or np.ndim(c) == 1 else nx
     Wa = arr(_cm(prob.W if W is None else W))
     wa = arr(prob.w if w is None else w)
     Fa = arr(_cm(prob.Fp if Fp is None else Fp)) if mp else None
     ha = arr(prob.hp if hp is None else hp) if mp else None
-    ca = arr(prob.c)
     xlb, xub, ulb, uub = arr(prob.xlb), arr(prob.xub), arr(prob.ulb), arr(prob.uub)
-    dims = _lib.OcpDims(nx, nu, prob.np, N, mp, prob.poly_stage)
+    sk = None
+    if skip is not None:
+        sk = np.ascontiguousarray(skip, dtype=np.int32)
+        if sk.shape != (batch,):
+            raise ValueError('skip must have one entry per instance')
+        keep.append(sk)
+    dims = _lib.OcpDims(nx, nu, prob.np, N, mp, prob.poly_stage, 1 if stg else 0)
     data = _lib.OcpData(
         A=_lib.ptr(Aa), B=_lib.ptr(Ba), c=_lib.ptr(ca), W=_lib.ptr(Wa), w=_lib.ptr(wa),
         xlb=_lib.ptr(xlb), xub=_lib.ptr(xub), ulb=_lib.ptr(ulb), uub=_lib.ptr(uub),
         Fp=_lib.ptr(Fa), hp=_lib.ptr(ha), x0=_lib.ptr(x0),
-        sA=0 if A is None else nx * nx, sB=0 if B is None else nx * nu, sc=0,
+        sA=sA, sB=sB, sc=sc,
         sW=0 if W is None else (N + 1) * nv * nv,
         sw=0 if w is None else (N + 1) * nv, sxb=0, sub=0, sFp=0 if Fp is None else mp * nv,
-        shp=0 if hp is None else mp, sx0=nx)
+        shp=0 if hp is None else mp, sx0=nx, skip=_lib.iptr(sk) if sk is not None else None)
     return dims, data, batch, keep
 
 
 def solve_ocp(prob, x0, w=None, hp=None, A=None, B=None, handle=None, want_duals=False, Fp=None,
-              W=None, route='auto', **opts):
+              W=None, route='auto', c=None, stage_models=None, skip=None, **opts):
     """Solve a batch on the GPU.  Returns OcpResult(x (b,N+1,nx), u (b,N,nu), theta (b,np),
     fval, exitflag, iterations, firstorderopt, constrviolation, mu[, pi, lam_x, lam_u, lam_p]).
+    A, B, c: one model (nx, nx) / (batch, nx, nx), or per-stage models (linear time-varying)
+    (N, nx, nx) / (batch, N, nx, nx) - see pack; per-stage models run on the structured kernel
+    only, in fp64.  skip: with per-stage models, instances left unsolved
+    (their rows of the result keep the zeros they are created with).
     route: 'auto' (structured kernel; condensed when the C ABI reports the dimensions
     unsupported), 'structured' (no condensed route) or 'condensed'."""
     if route not in ('auto', 'structured', 'condensed'):
         raise ValueError("route must be 'auto', 'structured' or 'condensed', not %r" % (route,))
     lib = _lib.load()
     h = handle or _default_handle()
-    dims, data, batch, keep = pack(prob, x0, w, hp, A, B, Fp, W)
+    dims, data, batch, keep = pack(prob, x0, w, hp, A, B, Fp, W, c, stage_models, skip)
     N, nx, nu, npar, mp = prob.N, prob.nx, prob.nu, prob.np, prob.mp
     x = np.zeros((batch, N + 1, nx)); u = np.zeros((batch, N, nu)); th = np.zeros((batch, npar))
     fval = np.zeros(batch); flag = np.zeros(batch, np.int32)
@@ -116,6 +174,8 @@ def solve_ocp(prob, x0, w=None, hp=None, A=None, B=None, handle=None, want_duals
                   lam_u=np.zeros((batch, N, 2, nu)), lam_p=np.zeros((batch, max(mp, 1))))
         duals = _lib.OcpDuals(*(_lib.ptr(dd[k]) for k in ('pi', 'lam_x', 'lam_u', 'lam_p')))
     if route == 'condensed':
+        if c is not None or dims.stage_models:
+            raise ValueError('condensed route: only x0 and hp may vary per instance')
         return solve_ocp_condensed(prob, x0, w, hp, A, B, handle, want_duals, Fp, W, **opts)
     o = _lib.options(**opts)
     rc = lib.bqp_solve_ocp_batched(h.value, C.byref(dims), batch, C.byref(data), C.byref(o),
@@ -123,7 +183,7 @@ def solve_ocp(prob, x0, w=None, hp=None, A=None, B=None, handle=None, want_duals
                                    _lib.iptr(flag), out, C.byref(duals) if duals else None)
     # the condensed route takes only x0 and hp per instance: anything else keeps the structured
     # solver's own error (an LDS fit failure is not a reason to change the algorithm)
-    condensable = all(v is None for v in (w, A, B, Fp, W)) and not want_duals
+    condensable = all(v is None for v in (w, A, B, Fp, W, c)) and not want_duals
     if rc == _lib.BQP_E_UNSUPPORTED and route == 'auto' and condensable and \
             not _lib.ocp_dims_supported(prob.nx, prob.nu, prob.np, prob.N, prob.mp):
         return solve_ocp_condensed(prob, x0, w, hp, A, B, handle, want_duals, Fp, W, **opts)

@@ -57,6 +57,7 @@ struct bqp_handle_s {
     int* mixed_flags = nullptr;   // the last mixed-mode solve's fp32-phase flags
     int* mixed_cont = nullptr;    // and its continuation's exit flags (bqp_debug_mixed_flags)
     int mixed_batch = 0;
+    int ocp_wpb = 0;              // instances per workgroup of the last structured solve (bqp_debug_ocp_wpb)
     int nmpc_rounds = 0;          // SQP rounds of the last bqp_nmpc_solve_batched_device
     int loop_rounds = -1;         // and of the last bqp_closed_loop_nmpc_device (-1: none yet)
 };
@@ -140,6 +141,12 @@ struct Stage : layout::Arena {
     void in(P* dev, const T* src, size_t n, T* back = nullptr) {
         *dev = nullptr;
         if (src && n) items.push_back({dev, src, back, take<T>(n)});
+    }
+    // n elements that are input and output (the call may leave some of them as they were): as out(),
+    // with the caller's contents copied to the device first.  A null host array is a plain out()
+    template <class T>
+    void inout(T** dev, size_t n, T* host, size_t align = alignof(T)) {
+        items.push_back({dev, n ? host : nullptr, host, take_aligned(sizeof(T) * n, align)});
     }
     // n elements copied to host by finish() unless host is null
     template <class T>
@@ -235,6 +242,12 @@ int bqp_destroy(bqp_handle h) {
     return BQP_OK;
 }
 
+int bqp_debug_ocp_wpb(bqp_handle h, int* wpb) {
+    if (!h || !wpb || h->ocp_wpb <= 0) return BQP_E_ARG;
+    *wpb = h->ocp_wpb;
+    return BQP_OK;
+}
+
 int bqp_debug_mixed_flags(bqp_handle h, int batch, int* flags) {
     if (!h || !flags || batch <= 0) return BQP_E_ARG;
     if (!h->mixed_flags || batch != h->mixed_batch) return BQP_E_ARG;
@@ -285,8 +298,21 @@ static int ocp_check(const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D) {
     if (D->sW != 0 && D->sW < (int64_t)(d->N + 1) * (d->nx + d->nu + d->np) * (d->nx + d->nu + d->np))
         return BQP_E_ARG;                                     // per-instance stage costs overlap
     if (D->sFp != 0 && D->sFp < (int64_t)d->n_poly * (d->nx + d->nu + d->np)) return BQP_E_ARG;
+    if (d->stage_models != 0 && d->stage_models != 1) return BQP_E_ARG;
+    if (d->stage_models) {
+        // per-stage models: a per-instance stride spans the instance's whole schedule
+        const int64_t N = d->N, nx = d->nx, nu = d->nu;
+        if (D->sA != 0 && D->sA < N * nx * nx) return BQP_E_ARG;
+        if (D->sB != 0 && D->sB < N * nx * nu) return BQP_E_ARG;
+        if (D->c && D->sc != 0 && D->sc < N * nx) return BQP_E_ARG;
+    } else if (D->skip) {
+        return BQP_E_UNSUPPORTED;
+    }
     return BQP_OK;
 }
+
+// elements of the model arrays A, B, c per instance: one model, or N of them (stage_models)
+static size_t ocp_model_blocks(const bqp_ocp_dims* d) { return d->stage_models ? (size_t)d->N : 1; }
 
 int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
                                  const bqp_ocp_data* D, const bqp_options* opt, double* x,
@@ -300,6 +326,10 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
     bqp_options o;
     resolve(opt, &o);
     if (o.precision < 0 || o.precision > 2) return BQP_E_ARG;
+    // per-stage models: fp64 instantiations only (their repair launch carries the per-stage
+    // models: the polish runs on the same Riccati routines as the solve)
+    const bool stg = d->stage_models == 1;
+    if (stg && o.precision != 0) return BQP_E_UNSUPPORTED;
     const bool f32 = o.precision == 1;     // fp32 instantiation (bqp_ocp_f32.hip)
     // fp32 phase, then fp64 from the fp32 iterate; long horizons only (N + 1 > 64, the
     // instantiations that carry the handoff): shorter ones are solved in fp64 alone
@@ -358,7 +388,7 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
         const Shared& S = single ? L32 : L64;
         const int shared_doubles = S.doubles;
         const int per_wave = single ? bqp::ocp_wave_lds_doubles_f32(N, nx, nu, np, mpad, fpi, false, S.hpsh, false, hinst)
-                                    : bqp::ocp_wave_lds_doubles(N, nx, nu, np, mpad, fpi, S.lng, S.hpsh, S.bndsh, hinst);
+                                    : bqp::ocp_wave_lds_doubles(N, nx, nu, np, mpad, fpi, S.lng, S.hpsh, S.bndsh, hinst, stg);
         // 160 KB per workgroup less the repair kernel's 256 B of static LDS (its
         // __syncthreads_or scratch): N = 50 at two instances per workgroup sits exactly there
         const size_t lds_budget = (160 * 1024 - 256) / (single ? sizeof(float) : sizeof(double));
@@ -377,6 +407,7 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
     int wpb = 1, wpb32 = 1;
     if (!fit_wpb(f32, wpb)) return BQP_E_UNSUPPORTED;
     if (mixed && !fit_wpb(true, wpb32)) return BQP_E_UNSUPPORTED;
+    h->ocp_wpb = wpb;
     // workspace: H, Fp, stats, the repair marks, the work-queue counters of the launches
     const layout::Work WL = work_layout(N, nv, mpad, batch);
     HIP_TRY(h->work.reserve(WL.bytes));
@@ -427,6 +458,8 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
     a.sA = D->sA; a.sB = D->sB; a.sc = D->sc; a.sw = D->sw; a.sxb = D->sxb; a.sub = D->sub;
     a.shp = D->shp; a.sx0 = D->sx0;
     if (fpi) { a.Fp_inst = D->Fp; a.sFp = D->sFp; }
+    a.stage_models = stg ? 1 : 0;
+    a.skip = stg ? D->skip : nullptr;
     a.x = x; a.u = u; a.theta = theta; a.fval = fval; a.exitflag = exitflag; a.stats = Sd;
     if (duals) {
         a.pi_out = duals->pi; a.lamx_out = duals->lam_x; a.lamu_out = duals->lam_u;
@@ -486,7 +519,7 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
     HIP_TRY(hipEventRecord(h->ev1, st));
     h->timed = true;
     h->launches = (mixed ? 3 : 1) + ((!f32 && a.polish > 0) ? 1 : 0);
-    if (out) HIP_TRY(bqp::launch_ocp_finalize(Sd, batch, out, st));
+    if (out) HIP_TRY(bqp::launch_ocp_finalize(Sd, batch, out, st, a.skip));
     return BQP_OK;
 }
 
@@ -496,9 +529,10 @@ static void stage_ocp_data(Stage& st, const bqp_ocp_dims* d, int batch, const bq
                            const double* x0, size_t nx0, bqp_ocp_data* Dd) {
     const size_t nx = d->nx, nu = d->nu, N = d->N, mp = d->n_poly, nv = nx + nu + d->np;
     *Dd = *D;
-    st.in(&Dd->A, D->A, span(batch, D->sA, nx * nx));
-    st.in(&Dd->B, D->B, span(batch, D->sB, nx * nu));
-    st.in(&Dd->c, D->c, span(batch, D->sc, nx));
+    const size_t nm = ocp_model_blocks(d);
+    st.in(&Dd->A, D->A, span(batch, D->sA, nm * nx * nx));
+    st.in(&Dd->B, D->B, span(batch, D->sB, nm * nx * nu));
+    st.in(&Dd->c, D->c, span(batch, D->sc, nm * nx));
     st.in(&Dd->W, D->W, span(batch, D->sW, (N + 1) * nv * nv));
     st.in(&Dd->w, D->w, span(batch, D->sw, (N + 1) * nv));
     st.in(&Dd->xlb, D->xlb, span(batch, D->sxb, (N + 1) * nx));
@@ -508,6 +542,7 @@ static void stage_ocp_data(Stage& st, const bqp_ocp_dims* d, int batch, const bq
     st.in(&Dd->Fp, D->Fp, span(batch, D->sFp, mp * nv));
     st.in(&Dd->hp, D->hp, span(batch, D->shp, mp));
     st.in(&Dd->x0, x0, nx0);
+    st.in(&Dd->skip, D->skip, (size_t)batch);
 }
 
 int bqp_solve_ocp_batched(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D,
@@ -526,18 +561,25 @@ int bqp_solve_ocp_batched(bqp_handle h, const bqp_ocp_dims* d, int batch, const 
     int* ed;
     bqp_output* od;
     bqp_ocp_duals dd = {};
-    st.out(&xd, B * (N + 1) * nx, x);
-    st.out(&ud, B * N * nu, u);
-    st.out(&td, B * np, theta);
-    st.out(&fd, B, fval);
+    // with skipped instances (per-stage models) the outputs are arrays updated in place: the
+    // caller's contents go to the device first, so that a skipped instance's come back as they were
+    const bool inout = D->skip != nullptr;
+    auto res = [&](auto** dev, size_t n, auto* host, size_t align) {
+        if (inout) st.inout(dev, n, host, align);
+        else st.out(dev, n, host, align);
+    };
+    res(&xd, B * (N + 1) * nx, x, alignof(double));
+    res(&ud, B * N * nu, u, alignof(double));
+    res(&td, B * np, theta, alignof(double));
+    res(&fd, B, fval, alignof(double));
     if (duals) {
-        st.out(&dd.pi, B * N * nx, duals->pi);
-        st.out(&dd.lam_x, B * (N + 1) * nx * 2, duals->lam_x);
-        st.out(&dd.lam_u, B * N * nu * 2, duals->lam_u);
-        st.out(&dd.lam_p, B * mp, duals->lam_p);
+        res(&dd.pi, B * N * nx, duals->pi, alignof(double));
+        res(&dd.lam_x, B * (N + 1) * nx * 2, duals->lam_x, alignof(double));
+        res(&dd.lam_u, B * N * nu * 2, duals->lam_u, alignof(double));
+        res(&dd.lam_p, B * mp, duals->lam_p, alignof(double));
     }
-    st.out(&ed, B, exitflag);
-    st.out(&od, B, out, 64);
+    res(&ed, B, exitflag, alignof(int));
+    res(&od, B, out, 64);
     BQP_TRY(st.commit(STAGE_SOLVE_SLACK));
     BQP_TRY(bqp_solve_ocp_batched_device(h, d, batch, &Dd, opt, xd, ud, td, fd, ed, out ? od : nullptr,
                                          duals ? &dd : nullptr, h->stream));
@@ -934,6 +976,7 @@ static int closed_loop_impl(bqp_handle h, const bqp_ocp_dims* d, int batch, cons
                             int* exitflag, void* stream) {
     if (!h || !cl || !x_init || !X || !U) return BQP_E_ARG;
     BQP_TRY(ocp_check(d, batch, D));
+    if (d->stage_models) return BQP_E_UNSUPPORTED;   // per-stage models: the plain solves only
     BQP_TRY(loop_check(cl, d->nx, d->nu));
     if (lw && (lw->q < 1 || lw->q > (1 << 20) || !lw->XL)) return BQP_E_ARG;
     DevScope ds(h->device);
@@ -1000,6 +1043,7 @@ static int closed_loop_host(bqp_handle h, const bqp_ocp_dims* d, int batch, cons
     if (!h || !cl || !x_init || !X || !U) return BQP_E_ARG;
     if (lw && (lw->q < 1 || lw->q > (1 << 20) || !lw->XL)) return BQP_E_ARG;
     BQP_TRY(ocp_check(d, batch, D));
+    if (d->stage_models) return BQP_E_UNSUPPORTED;   // per-stage models: the plain solves only
     // validate the loop description before sizing the staging buffers from it
     BQP_TRY(loop_check(cl, d->nx, d->nu));
     DevScope ds(h->device);
@@ -1055,6 +1099,7 @@ static int track_check(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp
     bqp_ocp_data Dc = *D;
     Dc.x0 = x_init;
     BQP_TRY(ocp_check(d, batch, &Dc));
+    if (d->stage_models) return BQP_E_UNSUPPORTED;   // per-stage models: the plain solves only
     if (cl->steps <= 0 || !cl->x_eq || !cl->u_eq) return BQP_E_ARG;
     if (cl->plant == BQP_PLANT_LINEAR) {
         if (tr->sAp < 0 || tr->sBp < 0 || tr->sdist < 0) return BQP_E_ARG;

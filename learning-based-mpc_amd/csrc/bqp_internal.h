@@ -75,6 +75,11 @@ struct OcpKernelArgs {
     // and polishes them
     int polish;
     int* pol_need;
+    // per-stage models (bqp_ocp_dims.stage_models = 1; fp64 solve launch only): A, B, c hold N
+    // blocks per instance (strides sA, sB, sc over whole schedules), and instances with
+    // skip[i] != 0 (may be null) leave at once without writing an output
+    int stage_models;
+    const int* skip;
 };
 
 bool ocp_supported(int nx, int nu, int np);
@@ -82,12 +87,12 @@ int ocp_rpl_for(int mp);
 int ocp_bpl_for(int N, int nx, int nu);
 int ocp_hand_floats(int N, int nx, int nu, int np, int mp);
 int ocp_wave_lds_doubles(int N, int nx, int nu, int np, int mpad, bool fpi, bool lng, bool hpsh,
-                         bool bndsh, bool hinst);
+                         bool bndsh, bool hinst, bool stg = false);
 int ocp_pstride(int ns);
 hipError_t launch_ocp(const OcpKernelArgs& a, int nx, int nu, int np, hipStream_t st, bool pol = false);
 // fp32 instantiation (bqp_ocp_f32.hip): LDS element count per instance (floats) and launch
 int ocp_wave_lds_doubles_f32(int N, int nx, int nu, int np, int mpad, bool fpi, bool lng,
-                             bool hpsh, bool bndsh, bool hinst);
+                             bool hpsh, bool bndsh, bool hinst, bool stg = false);
 hipError_t launch_ocp_f32(const OcpKernelArgs& a, int nx, int nu, int np, hipStream_t st, bool pol = false);
 hipError_t launch_ocp_prep(const double* W, const double* Fp, int nx, int nu, int np, int N,
                            int mp, int kp, int hstride, int mpad, double* Hout, double* Fout,
@@ -95,7 +100,8 @@ hipError_t launch_ocp_prep(const double* W, const double* Fp, int nx, int nu, in
 hipError_t launch_ocp_queue_zero(int* q, hipStream_t st);   // one work-queue counter to 0
 hipError_t launch_ocp_prep_h(const double* W, int64_t sW, int batch, int nx, int nu, int np,
                              int N, int hstride, double* Hout, hipStream_t st);
-hipError_t launch_ocp_finalize(const double* stats, int batch, void* out, hipStream_t st);
+hipError_t launch_ocp_finalize(const double* stats, int batch, void* out, hipStream_t st,
+                               const int* skip = nullptr);
 
 // Dense quadprog kernel arguments.
 struct DenseKernelArgs {

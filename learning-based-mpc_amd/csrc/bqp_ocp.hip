@@ -28,6 +28,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "bqp_internal.h"
 #include "bqp_lanes.h"
 #include "bqp_wave.h"
@@ -207,6 +209,12 @@ __host__ __device__ constexpr int pk_idx(int NS, int i, int j) {
     return i <= j ? i * NS - i * (i - 1) / 2 + (j - i) : j * NS - j * (j - 1) / 2 + (i - j);
 }
 
+// Per-stage models: stage k's block of the LDS table is [A_k | B_k | c_k], A_k and B_k column-major
+// as in the caller's arrays (nx rows: the theta rows of Abar = [A 0; 0 I], Bbar = [B; 0] are not
+// stored).  The stride is odd, so that lane k's reads of stage k's block spread over the banks.
+__host__ __device__ constexpr int stg_len(int NX, int NU) { return NX * NX + NX * NU + NX; }
+__host__ __device__ constexpr int stg_stride(int NX, int NU) { return stg_len(NX, NU) | 1; }
+
 // Exchange scalars between the two waves of an instance (slots of the LDS xch block).
 enum : int {
     X_CNT = 0,   // number of inequality rows (row wave, once)
@@ -251,7 +259,7 @@ struct QpLds {
     // hinst: per-instance stage-cost table (bqp_ocp_data.sW != 0) in the slot (short horizons)
     __host__ __device__ __forceinline__ static QpLds make(int N, int NX, int NU, int NP, int mpad, bool fpi = false,
                                           bool lng = false, bool hpsh = false, bool bndsh = false,
-                                          bool hinst = false) {
+                                          bool hinst = false, bool stg = false) {
         const int NS = NX + NP, NV = NS + NU, NB = NX + NU;
         QpLds o;
         int c = 0;
@@ -259,7 +267,9 @@ struct QpLds {
         o.K = c;      c += N * NU * NS;              // feedback K_k (row-major NU x NS)
         o.Lr = c;     c += N * NU * NU;              // factor of Rhat_k (nu = 1: its reciprocal)
         o.L0 = c;     c += NP * NP;                  // factor of P_0[theta, theta]
-        o.AB = c;     c += NS * NS + NS * NU + NS;   // Abar (row-major), Bbar, cbar
+        // stg (per-stage models, bqp_ocp_dims.stage_models): N blocks [A_k | B_k | c_k] of
+        // stg_stride doubles instead (the x rows only; long horizons read the caller's arrays)
+        o.AB = c;     c += stg ? (lng ? 0 : N * stg_stride(NX, NU)) : NS * NS + NS * NU + NS;   // Abar (row-major), Bbar, cbar
         o.xs = c;     c += (N + 1) * NS;             // s_k
         o.xu = c;     c += (N + 1) * NU;             // u_k (u_N = 0)
         o.qt_xpi = c; c += (N + 1) * NS;             // pi_k in the residuals, qhat_k in the solves
@@ -377,7 +387,11 @@ __device__ __forceinline__ bool hand_warm(const OcpKernelArgs& a, int inst) {
 // s part, by the operation sequence the entry has at G = 1.  A pass that reads a whole stage
 // vector another pass produced by entries reads it from LDS after a wave_sync or a barrier; a
 // pass that reads back its own entries needs neither.
-template <int NX, int NU, int NP, int SPL, bool POL, int G>
+// STG: per-stage models (bqp_ocp_dims.stage_models = 1; fp64, G = 1; solve and repair kernels - the
+// polish runs on factor / prep_iter / solve / stage_partials, which read the stage's model):
+// every read of Abar / Bbar / cbar is a read of stage k's model, from the instance's LDS table
+// (N + 1 <= 64) or from the caller's arrays in global memory (long horizons).
+template <int NX, int NU, int NP, int SPL, bool POL, int G, bool STG = false>
 __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, const QpLds& L,
                                            const real* Hs, int lane_w, int inst, int pslot) {
     const int lane = lane_w;
@@ -387,6 +401,10 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     constexpr int NV = NS + NU;
     constexpr int NB = NX + NU;
     static_assert(G == 1 || (SPL == 1 && lanes::compiled(NS, NU, G)), "lane groups: short horizons only");
+    static_assert(!STG || (G == 1 && sizeof(real) == 8), "per-stage models: fp64, G = 1");
+    // the sweeps carry the stage's model in their DPP form only; the plain form (fp32) reads the
+    // one model of the solve and must never be compiled into a per-stage instantiation
+    static_assert(!STG || SWEEP_DPP_FMAC, "per-stage models: the sweeps' DPP form only");
     constexpr int ES = lanes::entries_per_lane(NS, G);   // s-part entries per lane
     const int N = a.N, kp = a.kp, hstride = a.hstride;
     // the stage a lane serves (> N: none); j: second stage of the lane at SPL = 2
@@ -419,7 +437,23 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     }
 
     // ---------------- per-instance model -> LDS (Abar row-major, Bbar) ---------------------
-    {
+    // per-stage models: the instance's schedule (N blocks each of A, B, c)
+    const double* Ag = STG ? a.A + (int64_t)inst * a.sA : nullptr;
+    const double* Bg = STG ? a.B + (int64_t)inst * a.sB : nullptr;
+    const double* cg = (STG && a.c) ? a.c + (int64_t)inst * a.sc : nullptr;
+    constexpr int MW = stg_len(NX, NU), MST = stg_stride(NX, NU);
+    if constexpr (STG) {
+        if constexpr (!LNG) {
+            for (int t = lane; t < N * MW; t += WAVE) {
+                const int k = t / MW, e = t - k * MW;
+                real v;
+                if (e < NX * NX) v = Ag[(int64_t)k * (NX * NX) + e];
+                else if (e < NX * NX + NX * NU) v = Bg[(int64_t)k * (NX * NU) + (e - NX * NX)];
+                else v = cg ? cg[(int64_t)k * NX + (e - NX * NX - NX * NU)] : 0.0;
+                W[L.AB + k * MST + e] = v;
+            }
+        }
+    } else {
         const double* A = a.A + (int64_t)inst * a.sA;
         const double* B = a.B + (int64_t)inst * a.sB;
         if (lane < NS * NS) {
@@ -434,11 +468,37 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         if (lane < NS) W[L.AB + NS * NS + NS * NU + lane] = (lane < NX && a.c) ? a.c[(int64_t)inst * a.sc + lane] : 0.0;
     }
     wave_sync();
-    auto Abar = [&](int i, int j) __attribute__((always_inline)) -> real { return W[L.AB + i * NS + j]; };
-    auto Bbar = [&](int i, int j) __attribute__((always_inline)) -> real { return W[L.AB + NS * NS + i * NU + j]; };
+    // element e of stage k's block [A_k | B_k | c_k] (STG).  The stage index is clamped to the
+    // table: the passes also run their model terms on stage N, whose result they discard
+    auto mdl = [&](int k, int e) __attribute__((always_inline)) -> real {
+        const int km = k < N ? k : N - 1;
+        if constexpr (LNG) {
+            if (e < NX * NX) return (real)Ag[(int64_t)km * (NX * NX) + e];
+            if (e < NX * NX + NX * NU) return (real)Bg[(int64_t)km * (NX * NU) + (e - NX * NX)];
+            return cg ? (real)cg[(int64_t)km * NX + (e - NX * NX - NX * NU)] : real(0);
+        } else {
+            return W[L.AB + km * MST + e];
+        }
+    };
+    // Abar_k = [A_k 0; 0 I], Bbar_k = [B_k; 0], cbar_k = [c_k; 0]; k is unused without STG
+    auto Abar = [&](int k, int i, int j) __attribute__((always_inline)) -> real {
+        if constexpr (STG) {
+            if (i < NX && j < NX) return mdl(k, j * NX + i);
+            return i == j ? real(1) : real(0);
+        } else {
+            return W[L.AB + i * NS + j];
+        }
+    };
+    auto Bbar = [&](int k, int i, int j) __attribute__((always_inline)) -> real {
+        if constexpr (STG) return i < NX ? mdl(k, NX * NX + j * NX + i) : real(0);
+        else return W[L.AB + NS * NS + i * NU + j];
+    };
     // c from LDS at use (a register copy was carried through the loop: a scratch spill of the
     // DI kernel)
-    auto cb = [&](int i) __attribute__((always_inline)) -> real { return W[L.AB + NS * NS + NS * NU + i]; };
+    auto cb = [&](int k, int i) __attribute__((always_inline)) -> real {
+        if constexpr (STG) return i < NX ? mdl(k, NX * NX + NX * NU + i) : real(0);
+        else return W[L.AB + NS * NS + NS * NU + i];
+    };
     const double* wb = a.w ? a.w + (int64_t)inst * a.sw : nullptr;
     // linear cost term of stage k, internal index i ([x; theta; u] from external [x; u; theta])
     auto gterm = [&](int k, int i) __attribute__((always_inline)) -> real {
@@ -509,7 +569,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                     gs = fmax(gs, fabs(acc));
                     if (k < N) {
 #pragma unroll
-                        for (int c = 0; c < NS; ++c) MADD(acc, Abar(c, i), pn[c]);
+                        for (int c = 0; c < NS; ++c) MADD(acc, Abar(k, c, i), pn[c]);
                     }
                     if (k > 0) acc -= W[L.qt_xpi + k * NS + i];
                     W[L.rs + k * NS + i] = acc;
@@ -526,18 +586,18 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int i = 0; i < NU; ++i) {
                     real acc = gu[i];
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) MADD(acc, Bbar(c, i), pn[c]);
+                    for (int c = 0; c < NS; ++c) MADD(acc, Bbar(k, c, i), pn[c]);
                     W[L.ru + k * NU + i] = (k < N) ? acc : 0.0;
                 }
                 if (k < N) {
 #pragma unroll
                     for (int t = 0; t < ES; ++t) {
                         const int i = lanes::entry(NS, G, sl.g, t);
-                        real acc = cb(i) - W[L.xs + (k + 1) * NS + i];
+                        real acc = cb(k, i) - W[L.xs + (k + 1) * NS + i];
 #pragma unroll
-                        for (int c = 0; c < NS; ++c) MADD(acc, Abar(i, c), s[0][c]);
+                        for (int c = 0; c < NS; ++c) MADD(acc, Abar(k, i, c), s[0][c]);
 #pragma unroll
-                        for (int c = 0; c < NU; ++c) MADD(acc, Bbar(i, c), u[0][c]);
+                        for (int c = 0; c < NU; ++c) MADD(acc, Bbar(k, i, c), u[0][c]);
                         W[L.re + k * NS + i] = acc;
                         fe = fmax(fe, fabs(acc));
                     }
@@ -574,7 +634,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 real acc = gv[i];
                 if (k < N) {
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) MADD(acc, Abar(c, i), pn[c]);
+                    for (int c = 0; c < NS; ++c) MADD(acc, Abar(k, c, i), pn[c]);
                 }
                 if (k > 0) acc -= pi[j][i];
                 W[L.rs + k * NS + i] = acc;
@@ -583,17 +643,17 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             for (int i = 0; i < NU; ++i) {
                 real acc = gv[NS + i];
 #pragma unroll
-                for (int c = 0; c < NS; ++c) MADD(acc, Bbar(c, i), pn[c]);
+                for (int c = 0; c < NS; ++c) MADD(acc, Bbar(k, c, i), pn[c]);
                 W[L.ru + k * NU + i] = (k < N) ? acc : 0.0;
             }
             if (k < N) {
 #pragma unroll
                 for (int i = 0; i < NS; ++i) {
-                    real acc = cb(i) - W[L.xs + (k + 1) * NS + i];
+                    real acc = cb(k, i) - W[L.xs + (k + 1) * NS + i];
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) MADD(acc, Abar(i, c), s[j][c]);
+                    for (int c = 0; c < NS; ++c) MADD(acc, Abar(k, i, c), s[j][c]);
 #pragma unroll
-                    for (int c = 0; c < NU; ++c) MADD(acc, Bbar(i, c), u[j][c]);
+                    for (int c = 0; c < NU; ++c) MADD(acc, Bbar(k, i, c), u[j][c]);
                     if constexpr (!LNG) W[L.re + k * NS + i] = acc;
                     fe = fmax(fe, fabs(acc));
                 }
@@ -608,11 +668,11 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     bool rez = false;   // polish direction solves: zero dynamics residual (PC only)
     auto re_at = [&](int j, int k, int i) __attribute__((always_inline)) -> real {
         if constexpr (PC) { if (rez) return real(0); }
-        real acc = cb(i) - W[L.xs + (k + 1) * NS + i];
+        real acc = cb(k, i) - W[L.xs + (k + 1) * NS + i];
 #pragma unroll
-        for (int c = 0; c < NS; ++c) MADD(acc, Abar(i, c), s[j][c]);
+        for (int c = 0; c < NS; ++c) MADD(acc, Abar(k, i, c), s[j][c]);
 #pragma unroll
-        for (int c = 0; c < NU; ++c) MADD(acc, Bbar(i, c), u[j][c]);
+        for (int c = 0; c < NU; ++c) MADD(acc, Bbar(k, i, c), u[j][c]);
         return acc;
     };
 
@@ -718,36 +778,75 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             r = NS + x; c = NS + x + t;
         }
     };
-    auto Fab = [&](int a_, int r) __attribute__((always_inline)) -> real {
-        return r < NS ? Abar(a_, r) : Bbar(a_, r - NS);
-    };
-    real cf[VPL][NPK];                              // coefficient rows of this lane's values
+    // STG: the coefficients change with the stage.  They are formed per stage from columns r and
+    // c of F_k = [Abar_k Bbar_k] (x rows; the theta rows are unit rows), which travel with the
+    // stage's raw cost operands (HRaw) and so are fetched as far ahead as those
+    real cf[STG ? 1 : VPL][STG ? 1 : NPK];          // coefficient rows of this lane's values
     int vr[VPL], vc[VPL];
+    int fr[VPL], fc[VPL];                           // STG: table offsets of the two columns (< 0: a zero column)
 #pragma unroll
     for (int t = 0; t < VPL; ++t) {
         const int v = fql + 4 * t;
         int r = 0, c = 0;
         if (v < VAL) vrc(v, r, c);
         vr[t] = r; vc[t] = c;
-        int m = 0;
+        if constexpr (STG) {
+            // column q of [A_k | B_k] starts at q NX of the stage's block
+            fr[t] = r < NX ? r * NX : (r >= NS ? (NX + r - NS) * NX : -1);
+            fc[t] = c < NX ? c * NX : (c >= NS ? (NX + c - NS) * NX : -1);
+        } else {
+            // one model for the solve (the stage argument of Abar / Bbar is unused without STG)
+            auto Fab = [&](int a_, int r_) __attribute__((always_inline)) -> real {
+                return r_ < NS ? Abar(0, a_, r_) : Bbar(0, a_, r_ - NS);
+            };
+            int m = 0;
 #pragma unroll
-        for (int a_ = 0; a_ < NS; ++a_)
+            for (int a_ = 0; a_ < NS; ++a_)
 #pragma unroll
-            for (int b = a_; b < NS; ++b, ++m) {
-                real x = Fab(a_, r) * Fab(b, c);
-                if (a_ != b) x = fmar(Fab(b, r), Fab(a_, c), x);
-                cf[t][m] = (v < VAL) ? x : real(0);
-            }
+                for (int b = a_; b < NS; ++b, ++m) {
+                    real x = Fab(a_, r) * Fab(b, c);
+                    if (a_ != b) x = fmar(Fab(b, r), Fab(a_, c), x);
+                    cf[t][m] = (v < VAL) ? x : real(0);
+                }
+        }
     }
     // Ht entry (r, c) of stage k: raw cost entry, box diagonal, polytope term at kp; the raw
     // operands are prefetched one stage ahead and combined as (H + D) + FD
-    struct HRaw { real h[VPL], d[VPL]; };
+    struct HNoModel {};
+    struct HModel { real mr[VPL][NX], mc[VPL][NX]; };   // STG: x rows of columns r and c of F_k
+    struct HRaw : std::conditional_t<STG, HModel, HNoModel> { real h[VPL], d[VPL]; };
     auto load_h = [&](int k, HRaw& o) __attribute__((always_inline)) {
         BQP_HK(k);
 #pragma unroll
         for (int t = 0; t < VPL; ++t) {
             o.h[t] = BQP_HV(vr[t] * NV + vc[t]);
             o.d[t] = W[L.Dx + k * NV + vr[t]];
+            if constexpr (STG) {
+#pragma unroll
+                for (int a_ = 0; a_ < NX; ++a_) {
+                    const real xr = mdl(k, (fr[t] < 0 ? 0 : fr[t]) + a_);
+                    const real xc = mdl(k, (fc[t] < 0 ? 0 : fc[t]) + a_);
+                    o.mr[t][a_] = fr[t] < 0 ? real(0) : xr;
+                    o.mc[t][a_] = fc[t] < 0 ? real(0) : xc;
+                }
+            }
+        }
+    };
+    // STG: coefficient m = (a_, b) of value t from the stage's columns, the products and their
+    // order those of the one-model form above
+    auto cf_at = [&](const HRaw& o, int t, int a_, int b) __attribute__((always_inline)) -> real {
+        if constexpr (STG) {
+            auto Fr = [&](int i) __attribute__((always_inline)) -> real {
+                return i < NX ? o.mr[t][i < NX ? i : 0] : (vr[t] == i ? real(1) : real(0));
+            };
+            auto Fc = [&](int i) __attribute__((always_inline)) -> real {
+                return i < NX ? o.mc[t][i < NX ? i : 0] : (vc[t] == i ? real(1) : real(0));
+            };
+            real x = Fr(a_) * Fc(b);
+            if (a_ != b) x = fmar(Fr(b), Fc(a_), x);
+            return (fql + 4 * t < VAL) ? x : real(0);
+        } else {
+            return real(0);   // not used: the one-model form reads cf directly
         }
     };
     auto ht = [&](int k, const HRaw& o, int t) __attribute__((always_inline)) -> real {
@@ -786,12 +885,26 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
 #pragma unroll
             for (int t = 0; t < VPL; ++t) {
                 real sp0 = 0, sp1 = 0, sp2 = 0, sp3 = 0;
+                if constexpr (STG) {
+                    int m = 0;
+#pragma unroll
+                    for (int a_ = 0; a_ < NS; ++a_)
+#pragma unroll
+                        for (int b = a_; b < NS; ++b, ++m) {
+                            const real cm = cf_at(raw, t, a_, b);
+                            if ((m & 3) == 0) sp0 = fmar(cm, pu[m], sp0);
+                            if ((m & 3) == 1) sp1 = fmar(cm, pu[m], sp1);
+                            if ((m & 3) == 2) sp2 = fmar(cm, pu[m], sp2);
+                            if ((m & 3) == 3) sp3 = fmar(cm, pu[m], sp3);
+                        }
+                } else {
 #pragma unroll
                 for (int m = 0; m < NPK; ++m) {
                     if ((m & 3) == 0) sp0 = fmar(cf[t][m], pu[m], sp0);
                     if ((m & 3) == 1) sp1 = fmar(cf[t][m], pu[m], sp1);
                     if ((m & 3) == 2) sp2 = fmar(cf[t][m], pu[m], sp2);
                     if ((m & 3) == 3) sp3 = fmar(cf[t][m], pu[m], sp3);
+                }
                 }
                 mv[t] = ht(k, raw, t) + ((sp0 + sp1) + (sp2 + sp3));
             }
@@ -945,7 +1058,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int x = 0; x < NU; ++x) {
                     real v = 0.0;
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(c, x), wk[c]);
+                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(k, c, x), wk[c]);
                     W[L.bw + k * NU + x] = v;
                 }
 #pragma unroll
@@ -954,9 +1067,9 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                     real v = 0.0;
 #pragma unroll
                     for (int c = 0; c < NS; ++c) {
-                        real ph = Abar(c, i);
+                        real ph = Abar(k, c, i);
 #pragma unroll
-                        for (int x = 0; x < NU; ++x) MADD(ph, Bbar(c, x), Kk[x * NS + i]);
+                        for (int x = 0; x < NU; ++x) MADD(ph, Bbar(k, c, x), Kk[x * NS + i]);
                         MADD(v, ph, wk[c]);
                     }
                     W[L.wv + k * NS + i] = v;
@@ -986,7 +1099,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int x = 0; x < NU; ++x) {
                     real v = 0.0;
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(c, x), wk[c]);
+                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(k, c, x), wk[c]);
                     W[L.bw + k * NU + x] = v;
                 }
 #pragma unroll
@@ -994,9 +1107,9 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                     real v = 0.0;
 #pragma unroll
                     for (int c = 0; c < NS; ++c) {
-                        real ph = Abar(c, i);
+                        real ph = Abar(k, c, i);
 #pragma unroll
-                        for (int x = 0; x < NU; ++x) MADD(ph, Bbar(c, x), Kk[x * NS + i]);
+                        for (int x = 0; x < NU; ++x) MADD(ph, Bbar(k, c, x), Kk[x * NS + i]);
                         MADD(v, ph, wk[c]);
                     }
                     W[L.wv + k * NS + i] = v;
@@ -1141,7 +1254,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
 #pragma unroll
             for (int c = 0; c < NS; ++c) {
 #pragma unroll
-                for (int x = 0; x < NU; ++x) Bl[c][x] = Bbar(c, x);
+                for (int x = 0; x < NU; ++x) Bl[c][x] = STG ? real(0) : Bbar(0, c, x);
             }
             if constexpr (SWEEP_DPP_FMAC) {
             // fp64: the multiply-adds take the previous accumulator as a DPP operand
@@ -1152,13 +1265,39 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             real pv = W[L.pv + N * NS + lx];
             real Acol[NS];
 #pragma unroll
-            for (int c = 0; c < NS; ++c) Acol[c] = Abar(c, lx);
-            auto phi_b = [&](const real (&kc)[NU], real (&ph)[NS]) __attribute__((always_inline)) {
+            for (int c = 0; c < NS; ++c) Acol[c] = STG ? real(0) : Abar(0, c, lx);
+            // STG: column lx of Abar_k and Bbar_k (x rows) per stage, loaded with the stage's K
+            // column into the same two register sets
+            struct MB { real ac[NX], bl[NX][NU]; };
+            auto load_mb = [&](int k, MB& m) __attribute__((always_inline)) {
+                if constexpr (STG) {
+                    const int lc = lx < NX ? lx : 0;
+#pragma unroll
+                    for (int c = 0; c < NX; ++c) {
+                        const real v = mdl(k, lc * NX + c);
+                        m.ac[c] = lx < NX ? v : real(0);
+#pragma unroll
+                        for (int x = 0; x < NU; ++x) m.bl[c][x] = mdl(k, NX * NX + x * NX + c);
+                    }
+                }
+            };
+            auto phi_b = [&](const real (&kc)[NU], const MB& m, real (&ph)[NS]) __attribute__((always_inline)) {
 #pragma unroll
                 for (int c = 0; c < NS; ++c) {
+                    if constexpr (STG) {
+                        // Phi_k(c, lx) = Abar_k(c, lx) + Bbar_k(c, :) K_k(:, lx); theta rows: unit
+                        if (c < NX) {
+                            ph[c] = m.ac[c];
+#pragma unroll
+                            for (int x = 0; x < NU; ++x) ph[c] += m.bl[c][x] * kc[x];
+                        } else {
+                            ph[c] = (lx == c) ? real(1) : real(0);
+                        }
+                    } else {
                     ph[c] = Acol[c];
 #pragma unroll
                     for (int x = 0; x < NU; ++x) ph[c] += Bl[c][x] * kc[x];
+                    }
                 }
             };
             auto chain_b = [&](const real (&ph)[NS], real q) __attribute__((always_inline)) {
@@ -1177,29 +1316,34 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 q = W[L.qt_xpi + k * NS + lx];
             };
             real k0[NU], q0, k1[NU], q1;
+            MB m0, m1;
             load_k(N - 1, k0);
             load_q(N - 1, q0);
+            load_mb(N - 1, m0);
             load_k(max(N - 2, 0), k1);
             load_q(max(N - 2, 0), q1);
-            auto step_b = [&](int k, const real (&kc)[NU], real q) __attribute__((always_inline)) {
+            load_mb(max(N - 2, 0), m1);
+            auto step_b = [&](int k, const real (&kc)[NU], real q, const MB& m) __attribute__((always_inline)) {
                 real ph[NS];
-                phi_b(kc, ph);
+                phi_b(kc, m, ph);
                 chain_b(ph, q);
                 store_b(k);
             };
             for (int k = N - 1; k >= 1; k -= 2) {
-                step_b(k, k0, q0);
+                step_b(k, k0, q0, m0);
                 load_k(max(k - 2, 0), k0);
                 load_q(max(k - 2, 0), q0);
-                step_b(k - 1, k1, q1);
+                load_mb(max(k - 2, 0), m0);
+                step_b(k - 1, k1, q1, m1);
                 load_k(max(k - 3, 0), k1);
                 load_q(max(k - 3, 0), q1);
+                load_mb(max(k - 3, 0), m1);
             }
-            if (N & 1) step_b(0, k0, q0);
+            if (N & 1) step_b(0, k0, q0, m0);
             } else {
             real Acol[NS];
 #pragma unroll
-            for (int c = 0; c < NS; ++c) Acol[c] = Abar(c, li);
+            for (int c = 0; c < NS; ++c) Acol[c] = Abar(0, c, li);
             auto load_b = [&](int k, real (&kc)[NU], real& q) __attribute__((always_inline)) {
                 q = W[L.qt_xpi + k * NS + li];
 #pragma unroll
@@ -1255,7 +1399,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int x = 0; x < NU; ++x) {
                     real v = qu[0][x] + W[L.bw + k * NU + x];
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(c, x), y[c]);
+                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(k, c, x), y[c]);
                     r[x] = -v;
                 }
                 chol_solve_small<NU>(W + L.Lr + k * NU * NU, r);
@@ -1266,7 +1410,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                     const int i = lanes::entry(NS, G, sl.g, t);
                     real v = W[L.re + k * NS + i];
 #pragma unroll
-                    for (int x = 0; x < NU; ++x) MADD(v, Bbar(i, x), kff[0][x]);
+                    for (int x = 0; x < NU; ++x) MADD(v, Bbar(k, i, x), kff[0][x]);
                     W[L.fv + k * NS + i] = v;
                 }
             }
@@ -1282,7 +1426,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int x = 0; x < NU; ++x) {
                     real v = qu[j][x] + W[L.bw + k * NU + x];
 #pragma unroll
-                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(c, x), y[c]);
+                    for (int c = 0; c < NS; ++c) MADD(v, Bbar(k, c, x), y[c]);
                     r[x] = -v;
                 }
                 chol_solve_small<NU>(W + L.Lr + k * NU * NU, r);
@@ -1292,7 +1436,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int i = 0; i < NS; ++i) {
                     real v = LNG ? re_at(j, k, i) : W[L.re + k * NS + i];
 #pragma unroll
-                    for (int x = 0; x < NU; ++x) MADD(v, Bbar(i, x), kff[j][x]);
+                    for (int x = 0; x < NU; ++x) MADD(v, Bbar(k, i, x), kff[j][x]);
                     W[L.fv + k * NS + i] = v;
                 }
             }
@@ -1331,15 +1475,33 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             for (int x = 0; x < NP; ++x) dv = (lx == NX + x) ? r0[x] : dv;
             real Arow[NS], Bli[NU];
 #pragma unroll
-            for (int c = 0; c < NS; ++c) Arow[c] = Abar(lx, c);
+            for (int c = 0; c < NS; ++c) Arow[c] = STG ? real(0) : Abar(0, lx, c);
 #pragma unroll
-            for (int x = 0; x < NU; ++x) Bli[x] = Bbar(lx, x);
-            auto phi_f = [&](const real (&kr)[NU][NS], real (&ph)[NS]) __attribute__((always_inline)) {
+            for (int x = 0; x < NU; ++x) Bli[x] = STG ? real(0) : Bbar(0, lx, x);
+            // STG: row lx of Abar_k and Bbar_k per stage (theta rows: unit row, zero), loaded with
+            // the stage's K into the same two register sets
+            struct MF { real ar[NS], bl[NU]; };
+            auto load_mf = [&](int k, MF& m) __attribute__((always_inline)) {
+                if constexpr (STG) {
+                    const int lr = lx < NX ? lx : 0;
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) {
+                        const real v = c < NX ? mdl(k, c * NX + lr) : real(0);
+                        m.ar[c] = lx < NX ? v : (lx == c ? real(1) : real(0));
+                    }
+#pragma unroll
+                    for (int x = 0; x < NU; ++x) {
+                        const real v = mdl(k, NX * NX + x * NX + lr);
+                        m.bl[x] = lx < NX ? v : real(0);
+                    }
+                }
+            };
+            auto phi_f = [&](const real (&kr)[NU][NS], const MF& m, real (&ph)[NS]) __attribute__((always_inline)) {
 #pragma unroll
                 for (int c = 0; c < NS; ++c) {
-                    ph[c] = Arow[c];
+                    ph[c] = STG ? m.ar[c] : Arow[c];
 #pragma unroll
-                    for (int x = 0; x < NU; ++x) ph[c] += Bli[x] * kr[x][c];
+                    for (int x = 0; x < NU; ++x) ph[c] += (STG ? m.bl[x] : Bli[x]) * kr[x][c];
                 }
             };
             auto chain_f = [&](const real (&ph)[NS], real f) __attribute__((always_inline)) {
@@ -1355,31 +1517,36 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             };
             // unconditional refills (stage index clamped at N - 1) and whole stage pairs, as in
             // the backward sweep
+            MF m0, m1;
             load_k(0, k0);
             load_fk(0, f0);
+            load_mf(0, m0);
             load_k(min(1, N - 1), k1);
             load_fk(min(1, N - 1), f1);
-            auto step_f = [&](int k, const real (&kr)[NU][NS], real f) __attribute__((always_inline)) {
+            load_mf(min(1, N - 1), m1);
+            auto step_f = [&](int k, const real (&kr)[NU][NS], real f, const MF& m) __attribute__((always_inline)) {
                 real ph[NS];
-                phi_f(kr, ph);
+                phi_f(kr, m, ph);
                 chain_f(ph, f);
                 store_f(k);
             };
             for (int k = 0; k + 1 < N; k += 2) {
-                step_f(k, k0, f0);
+                step_f(k, k0, f0, m0);
                 load_k(min(k + 2, N - 1), k0);
                 load_fk(min(k + 2, N - 1), f0);
-                step_f(k + 1, k1, f1);
+                load_mf(min(k + 2, N - 1), m0);
+                step_f(k + 1, k1, f1, m1);
                 load_k(min(k + 3, N - 1), k1);
                 load_fk(min(k + 3, N - 1), f1);
+                load_mf(min(k + 3, N - 1), m1);
             }
-            if (N & 1) step_f(N - 1, k0, f0);
+            if (N & 1) step_f(N - 1, k0, f0, m0);
             } else {
             real Arow[NS], Bli[NU];
 #pragma unroll
-            for (int c = 0; c < NS; ++c) Arow[c] = Abar(li, c);
+            for (int c = 0; c < NS; ++c) Arow[c] = Abar(0, li, c);
 #pragma unroll
-            for (int x = 0; x < NU; ++x) Bli[x] = Bbar(li, x);
+            for (int x = 0; x < NU; ++x) Bli[x] = Bbar(0, li, x);
             auto load_f = [&](int k, real (&kr)[NU][NS], real& f) __attribute__((always_inline)) {
                 f = W[L.fv + k * NS + li];
                 load_k(k, kr);
@@ -2972,7 +3139,7 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
 // ==========================================================================================
 // kernel: QPB instances per workgroup, waves [0, QPB) stage waves, [QPB, 2 QPB) row waves
 // ==========================================================================================
-template <int NX, int NU, int NP, int SPL, int RPL, int BPL, bool POL, bool QUEUE, int G>
+template <int NX, int NU, int NP, int SPL, int RPL, int BPL, bool POL, bool QUEUE, int G, bool STG = false>
 __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
     constexpr int NS = NX + NP;
     constexpr int NV = NS + NU;
@@ -2986,7 +3153,9 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
         // repair launch: a workgroup none of whose instances the solve launch marked leaves
         // before staging the shared tables
         const int i0 = blockIdx.x * a.wpb + ((threadIdx.x >> 6) % a.wpb);
-        const bool need = i0 < a.batch && a.pol_need[i0] != 0;
+        bool need = i0 < a.batch && a.pol_need[i0] != 0;
+        // a skipped instance's mark is left over from an earlier call
+        if constexpr (STG) { if (need && a.skip && a.skip[i0] != 0) need = false; }
         if (!__syncthreads_or(need)) return;
     }
     // ---------------- shared tables: H (N+1 stages) and Fp (column-major, mpad rows) -------
@@ -3064,7 +3233,7 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
     // ticket of the slot's next instance into the exchange word xnext first
     auto instance = [&](int inst, int slot, int lane, int xnext) __attribute__((always_inline)) {
         const QpLds L = QpLds::make(N, NX, NU, NP, a.mpad, fpi, LNG, a.sh_hp >= 0,
-                                    LNG && a.sh_bnd >= 0, a.H_inst != nullptr);
+                                    LNG && a.sh_bnd >= 0, a.H_inst != nullptr, STG);
         real* W = lds + a.shared_doubles + slot * L.total;
         real* Fsi = Fs;
         if (fpi && rowwave) {
@@ -3086,11 +3255,11 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
         if (rowwave && lane == 0)
             *reinterpret_cast<int*>(W + L.xch + X_NEXT + xnext) = atomicAdd(a.queue, 1) + (int)gridDim.x * qpb;
 #if defined(BQP_EXP_ONLY)   // register-budget diagnostic: one wave's code alone (never run)
-        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL, G>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
+        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL, G, STG>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
         else row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fsi, lds, lane, inst);
 #else
         if (!rowwave)
-            stage_wave<NX, NU, NP, SPL, POL, G>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
+            stage_wave<NX, NU, NP, SPL, POL, G, STG>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
         else
             row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fsi, lds, lane, inst);
 #endif
@@ -3103,10 +3272,14 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
         if (!POL && SPL == 2 && a.redo_flag &&
             !(a.exitflag[inst] != 1 && (a.redo_flag[inst] == 1 || a.redo_flag[inst] == 0)))
             return;                        // mixed mode, cold retry launch: nothing to redo here
+        // per-stage models: an instance the caller marks leaves at once (both waves of its slot,
+        // before their first barrier) and writes none of its outputs
+        // (also in the repair launch: a skipped instance's mark is left over from an earlier call)
+        if constexpr (STG) { if (a.skip && a.skip[inst] != 0) return; }
         const int slot = slot0;
         const int lane = lane_k;
         const QpLds L = QpLds::make(N, NX, NU, NP, a.mpad, fpi, LNG, a.sh_hp >= 0,
-                                    LNG && a.sh_bnd >= 0, a.H_inst != nullptr);
+                                    LNG && a.sh_bnd >= 0, a.H_inst != nullptr, STG);
         real* W = lds + a.shared_doubles + slot * L.total;
         if (fpi && rowwave) {
             // the instance's polytope, external column-major [x; u; theta] (n_poly rows) -> internal
@@ -3125,11 +3298,11 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
             wave_sync();
         }
 #if defined(BQP_EXP_ONLY)   // register-budget diagnostic: one wave's code alone (never run)
-        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL, G>(a, W, L, Hs, lane, inst, inst);
+        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL, G, STG>(a, W, L, Hs, lane, inst, inst);
         else row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fs, lds, lane, inst);
 #else
         if (!rowwave)
-            stage_wave<NX, NU, NP, SPL, POL, G>(a, W, L, Hs, lane, inst, inst);
+            stage_wave<NX, NU, NP, SPL, POL, G, STG>(a, W, L, Hs, lane, inst, inst);
         else
             row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fs, lds, lane, inst);
 #endif
@@ -3170,13 +3343,15 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
 // the solve kernel (no polish code: the main loop keeps its register budget), the repair kernel
 // (same IPM, then the active-set polish) over the instances the solve kernel marked, and the
 // persistent solve kernel (work queue) for batches beyond the resident workgroups
-template <int NX, int NU, int NP, int SPL, int RPL, int BPL, int G>
+// (STG: per-stage models, bqp_ocp_dims.stage_models = 1 - solve and repair kernels; batches beyond
+// the resident workgroups run as one instance per slot, not on the persistent kernel)
+template <int NX, int NU, int NP, int SPL, int RPL, int BPL, int G, bool STG = false>
 __global__ void __launch_bounds__(SPL == 2 ? 256 : 512) ocp_ipm_kernel(OcpKernelArgs a) {
-    ocp_body<NX, NU, NP, SPL, RPL, BPL, false, false, G>(a);
+    ocp_body<NX, NU, NP, SPL, RPL, BPL, false, false, G, STG>(a);
 }
-template <int NX, int NU, int NP, int SPL, int RPL, int BPL, int G>
+template <int NX, int NU, int NP, int SPL, int RPL, int BPL, int G, bool STG = false>
 __global__ void __launch_bounds__(SPL == 2 ? 256 : 512) ocp_polish_kernel(OcpKernelArgs a) {
-    ocp_body<NX, NU, NP, SPL, RPL, BPL, true, false, G>(a);
+    ocp_body<NX, NU, NP, SPL, RPL, BPL, true, false, G, STG>(a);
 }
 #ifndef BQP_DI_OCC3
 #define BQP_DI_OCC3 0
@@ -3198,15 +3373,38 @@ ocp_queue_kernel(OcpKernelArgs a) {
 // The kernel instantiations are split over translation units by model family so that the
 // build compiles them in parallel (Makefile: BQP_FAMILY=1 MG nx4/nu1/np1 with the dispatcher
 // and host helpers, BQP_FAMILY=2 DI nx2/nu2/np2); without BQP_FAMILY one unit holds all.
+// The per-stage-model instantiations (fp64 only) are units of their own: BQP_FAMILY=3 MG, 4 DI.
 #if !defined(BQP_FAMILY)
 #define BQP_FAM_MG 1
 #define BQP_FAM_DI 1
+#define BQP_FAM_STG_MG 1
+#define BQP_FAM_STG_DI 1
 #elif BQP_FAMILY == 1
 #define BQP_FAM_MG 1
 #define BQP_FAM_DI 0
-#else
+#elif BQP_FAMILY == 2
 #define BQP_FAM_MG 0
 #define BQP_FAM_DI 1
+#elif BQP_FAMILY == 3
+#define BQP_FAM_MG 0
+#define BQP_FAM_DI 0
+#define BQP_FAM_STG_MG 1
+#else
+#define BQP_FAM_MG 0
+#define BQP_FAM_DI 0
+#define BQP_FAM_STG_DI 1
+#endif
+#ifndef BQP_FAM_STG_MG
+#define BQP_FAM_STG_MG 0
+#endif
+#ifndef BQP_FAM_STG_DI
+#define BQP_FAM_STG_DI 0
+#endif
+#if defined(BQP_F32) || defined(BQP_ISA_ONLY_MG10) || defined(BQP_ISA_ONLY_MG_LNG) || defined(BQP_ISA_ONLY_DI)
+#undef BQP_FAM_STG_MG
+#undef BQP_FAM_STG_DI
+#define BQP_FAM_STG_MG 0
+#define BQP_FAM_STG_DI 0
 #endif
 
 // dynamic LDS of a launch: the kernel's static LDS must fit beside it (a launch past 160 KB is
@@ -3305,6 +3503,51 @@ static hipError_t launch_spl(const OcpKernelArgs& a, int spl, int rpl, int block
     return hipErrorInvalidValue;
 }
 
+// per-stage models (OcpKernelArgs::stage_models): one instance per slot over the whole batch, no
+// lane groups, no persistent kernel
+template <int NX, int NU, int NP, int SPL, int BPL>
+[[maybe_unused]] static hipError_t launch_stg_rpl(const OcpKernelArgs& a0, int rpl, int blocks, size_t lds, hipStream_t st, bool pol) {
+#ifndef BQP_F32
+    OcpKernelArgs a = a0;
+    a.queue = nullptr;
+    auto go = [&](auto k) -> hipError_t {
+        if (hipError_t e = lds_attr((const void*)k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(blocks), dim3(128 * a.wpb), lds, st, a);
+        return hipGetLastError();
+    };
+    switch (rpl) {
+        case 1: return pol ? go(dp::ocp_polish_kernel<NX, NU, NP, SPL, 1, BPL, 1, true>) : go(dp::ocp_ipm_kernel<NX, NU, NP, SPL, 1, BPL, 1, true>);
+        case 4: return pol ? go(dp::ocp_polish_kernel<NX, NU, NP, SPL, 4, BPL, 1, true>) : go(dp::ocp_ipm_kernel<NX, NU, NP, SPL, 4, BPL, 1, true>);
+        case 10: return pol ? go(dp::ocp_polish_kernel<NX, NU, NP, SPL, 10, BPL, 1, true>) : go(dp::ocp_ipm_kernel<NX, NU, NP, SPL, 10, BPL, 1, true>);
+        case 16: return pol ? go(dp::ocp_polish_kernel<NX, NU, NP, SPL, 16, BPL, 1, true>) : go(dp::ocp_ipm_kernel<NX, NU, NP, SPL, 16, BPL, 1, true>);
+        default: return hipErrorInvalidValue;
+    }
+#else
+    return hipErrorInvalidValue;
+#endif
+}
+template <int NX, int NU, int NP>
+[[maybe_unused]] static hipError_t launch_stg_spl(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st, bool pol) {
+    const int nbr = (a.N + 1) * 2 * (NX + NU);
+    if (spl == 1 && nbr <= 4 * WAVE) return launch_stg_rpl<NX, NU, NP, 1, 4>(a, rpl, blocks, lds, st, pol);
+    if (spl == 1 && nbr <= 10 * WAVE) return launch_stg_rpl<NX, NU, NP, 1, 10>(a, rpl, blocks, lds, st, pol);
+    if (spl == 2 && nbr <= 16 * WAVE) return launch_stg_rpl<NX, NU, NP, 2, 16>(a, rpl, blocks, lds, st, pol);
+    if (spl == 2 && nbr <= 20 * WAVE) return launch_stg_rpl<NX, NU, NP, 2, 20>(a, rpl, blocks, lds, st, pol);
+    return hipErrorInvalidValue;
+}
+hipError_t launch_ocp_stg_mg(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st, bool pol);
+hipError_t launch_ocp_stg_di(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st, bool pol);
+#if BQP_FAM_STG_MG
+hipError_t launch_ocp_stg_mg(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st, bool pol) {
+    return launch_stg_spl<4, 1, 1>(a, spl, rpl, blocks, lds, st, pol);
+}
+#endif
+#if BQP_FAM_STG_DI
+hipError_t launch_ocp_stg_di(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st, bool pol) {
+    return launch_stg_spl<2, 2, 2>(a, spl, rpl, blocks, lds, st, pol);
+}
+#endif
+
 hipError_t BQP_CAT(launch_ocp_mg, BQP_SFX)(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st, bool pol);
 hipError_t BQP_CAT(launch_ocp_di, BQP_SFX)(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st, bool pol);
 
@@ -3370,11 +3613,11 @@ int ocp_hand_floats(int N, int nx, int nu, int np, int mp) {
 
 // LDS elements (of the instantiation's precision) per instance
 int BQP_CAT(ocp_wave_lds_doubles, BQP_SFX)(int N, int nx, int nu, int np, int mpad, bool fpi,
-                                          bool lng, bool hpsh, bool bndsh, bool hinst) {
+                                          bool lng, bool hpsh, bool bndsh, bool hinst, bool stg) {
 #ifdef BQP_F32
-    return sp::QpLds::make(N, nx, nu, np, mpad, fpi, lng, hpsh, bndsh, hinst).total;
+    return sp::QpLds::make(N, nx, nu, np, mpad, fpi, lng, hpsh, bndsh, hinst, stg).total;
 #else
-    return dp::QpLds::make(N, nx, nu, np, mpad, fpi, lng, hpsh, bndsh, hinst).total;
+    return dp::QpLds::make(N, nx, nu, np, mpad, fpi, lng, hpsh, bndsh, hinst, stg).total;
 #endif
 }
 
@@ -3387,7 +3630,17 @@ hipError_t BQP_CAT(launch_ocp, BQP_SFX)(const OcpKernelArgs& a, int nx, int nu, 
                                                                                       a.Fp_inst != nullptr, BQP_LNG_OK && spl == 2,
                                                                                       a.sh_hp >= 0,
                                                                                       BQP_LNG_OK && spl == 2 && a.sh_bnd >= 0,
-                                                                                      a.H_inst != nullptr));
+                                                                                      a.H_inst != nullptr,
+                                                                                      a.stage_models != 0));
+#if !defined(BQP_F32) && !defined(BQP_ISA_ONLY_MG10) && !defined(BQP_ISA_ONLY_MG_LNG) && !defined(BQP_ISA_ONLY_DI)
+    if (a.stage_models) {
+        if (nx == 4 && nu == 1 && np == 1) return launch_ocp_stg_mg(a, spl, rpl, blocks, lds, st, pol);
+        if (nx == 2 && nu == 2 && np == 2) return launch_ocp_stg_di(a, spl, rpl, blocks, lds, st, pol);
+        return hipErrorInvalidValue;
+    }
+#else
+    if (a.stage_models) return hipErrorInvalidValue;
+#endif
     if (nx == 4 && nu == 1 && np == 1) return BQP_CAT(launch_ocp_mg, BQP_SFX)(a, spl, rpl, blocks, lds, st, pol);
 #if !defined(BQP_ISA_ONLY_MG10) && !defined(BQP_ISA_ONLY_MG_LNG)
     if (nx == 2 && nu == 2 && np == 2) return BQP_CAT(launch_ocp_di, BQP_SFX)(a, spl, rpl, blocks, lds, st, pol);

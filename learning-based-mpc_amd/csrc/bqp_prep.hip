@@ -102,9 +102,11 @@ hipError_t launch_ocp_prep_h(const double* W, int64_t sW, int batch, int nx, int
     return hipGetLastError();
 }
 
-__global__ void finalize_kernel(const double* __restrict__ stats, int batch, bqp_output* out) {
+__global__ void finalize_kernel(const double* __restrict__ stats, int batch, bqp_output* out,
+                                const int* __restrict__ skip) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
+    if (skip && skip[b] != 0) return;   // an unsolved instance: its record stays as it is
     const double* s = stats + (size_t)b * STATS_W;
     bqp_output o;
     o.iterations = (int)s[0];
@@ -119,9 +121,10 @@ __global__ void finalize_kernel(const double* __restrict__ stats, int batch, bqp
     out[b] = o;
 }
 
-hipError_t launch_ocp_finalize(const double* stats, int batch, void* out, hipStream_t st) {
+hipError_t launch_ocp_finalize(const double* stats, int batch, void* out, hipStream_t st,
+                               const int* skip) {
     hipLaunchKernelGGL(finalize_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, stats, batch,
-                       (bqp_output*)out);
+                       (bqp_output*)out, skip);
     return hipGetLastError();
 }
 

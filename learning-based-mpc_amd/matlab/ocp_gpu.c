@@ -91,6 +91,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!mxIsDouble(X0) || mxIsComplex(X0)) mexErrMsgIdAndTxt("bqp:args", "x0 must be a real double array");
     const mxArray* A = field(P, "A", 1);
     bqp_ocp_dims d;
+    memset(&d, 0, sizeof(d));   /* stage_models = 0: P.A, P.B, P.c are one model for the horizon */
     d.nx = (int)mxGetM(A);
     d.N = scalar_int(P, "N");
     d.nu = scalar_int(P, "nu");
