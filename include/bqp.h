@@ -459,6 +459,26 @@ typedef struct {
     int N;        /* horizon, 1..127 */
     int mx, mu;   /* rows of F_x (<= 32) and F_u (<= 8) */
     int n_poly;   /* rows of F_T */
+    int subproblem; /* how the SQP's sub-problems are solved.  0 (a zero-initialised caller): the
+                       dense route above - condensed H, f and the instance's own C on the dense
+                       kernels.  1: the stage route - the sub-problem stays in stage form, a linear
+                       time-varying tracking QP in v_k = [dx_k; du_k; dtheta] with the rollout's
+                       A_k, B_k (dx_0 = 0), the tracking cost's W_k shared by the batch, plain
+                       bounds on dx_k and du_k and the terminal rows on [dx_N; dtheta], solved by
+                       bqp_solve_ocp_batched_device with stage_models = 1; neither H nor C is
+                       formed.  The stage route needs box rows: every row of F_x and of F_u has
+                       exactly one non-zero entry and each (variable, side) at most one row; a
+                       positive scale is allowed (a x_i <= h is the bound h / a, its multiplier
+                       lam_bound / a).  Anything else returns BQP_E_UNSUPPORTED (the _device
+                       entries read one flag back from the device for it before the first
+                       round), as does an n_poly outside the structured kernel's compiled row
+                       counts.  lam, exitflag, iterations and cost mean what they mean on the
+                       dense route.  opt->polish goes to the structured solve as that solve
+                       defines it (bqp_options.polish: 0 / 1 after a 0 / -8 exit, 2 also on a
+                       weakly active row, -1 off; 3, the SQP routines' "after a stall", is taken
+                       as 2 from the first iteration).  Honoured by bqp_nmpc_solve_batched[_device] and
+                       bqp_closed_loop_nmpc[_device] in both loop modes; bqp_nmpc_linearize
+                       ignores it.  Any other value is BQP_E_ARG */
 } bqp_nmpc_dims;
 
 typedef struct {
@@ -483,11 +503,27 @@ int bqp_nmpc_linearize_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
                               const bqp_nmpc_data* data, const double* z, double* X, double* cost,
                               double* c, double* C, double* H, double* f, void* stream);
 
+/* The stage sub-problem at given z (batch*n), as the stage route (subproblem = 1) hands it to the
+ * structured solve - the diagnostic counterpart of bqp_nmpc_linearize; d->subproblem is not read,
+ * the box-row restriction of the stage route applies.  Outputs, each may be NULL: A (batch*N*16,
+ * column-major 4 x 4 blocks), B (batch*N*4), w (batch*(N+1)*6), xlb / xub (batch*(N+1)*4; stage 0
+ * is -inf / +inf), ulb / uub (batch*N), hp (batch*n_poly), and the shared W ((N+1)*36) and
+ * Fp (n_poly*6, column-major). */
+int bqp_nmpc_stage_qp(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
+                      const double* z, double* A, double* B, double* w, double* xlb, double* xub,
+                      double* ulb, double* uub, double* hp, double* W, double* Fp);
+int bqp_nmpc_stage_qp_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                             const bqp_nmpc_data* data, const double* z, double* A, double* B,
+                             double* w, double* xlb, double* xub, double* ulb, double* uub,
+                             double* hp, double* W, double* Fp, void* stream);
+
 /* SQP solve.  z (batch*n): in = start, out = solution; lam (batch*m, may be NULL): multipliers
  * of the rows above; cost (batch, may be NULL); exitflag: 1 converged, 0 iteration limit
  * (opt->max_iter SQP iterations), -2 sub-problem infeasible, -8 numerical failure (a non-finite
- * accepted iterate included).  The workspace holds every instance's C (m*n doubles: 1.3 MB at
- * N = 100 with 616 terminal rows); a batch that does not fit returns BQP_E_HIP.  The sub-problems
+ * accepted iterate included).  With subproblem = 0 the workspace holds every instance's C (m*n
+ * doubles: 1.3 MB at N = 100 with 616 terminal rows); a batch that does not fit returns
+ * BQP_E_HIP.  The stage route (subproblem = 1) keeps 79 KB per instance at N = 100 (325 MB for 4,096).  On the
+ * dense route the sub-problems
  * are polished only with opt->polish > 0 (modes as bqp_lbmpc_solve_batched): on the warm starts
  * of the closed loop, which lie on active state rows, the polish can fail.  The _device
  * variant synchronises its stream while it polls for the batch's convergence. */
@@ -512,7 +548,8 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
  * forms do the same operations in the same order and return the same bits.  steps = 0 is allowed
  * and returns X = x_init.  X (batch*(steps+1)*4), U (batch*steps) absolute; exitflag and iterations
  * (batch*steps, may be NULL) per solve.  The loop's time goes to bqp_last_kernel_ms (6 launches
- * per round), its rounds to bqp_last_loop_rounds.  The _device variant synchronises its stream
+ * per round; on the stage route 6 and the structured solve's repair launch where opt->polish
+ * asks for one), its rounds to bqp_last_loop_rounds.  The _device variant synchronises its stream
  * while it polls for the instances that have finished. */
 int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
                          const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,
@@ -528,7 +565,8 @@ int bqp_last_kernel_ms(bqp_handle h, double* ms, int* launches);
 
 /* SQP rounds that the most recent bqp_closed_loop_nmpc[_device] on this handle launched, in either
  * of its modes; a round is one launch of rollout, normal equations, dense sub-problem, trial
- * rollouts and update.  BQP_E_ARG before any such loop has run on the handle. */
+ * rollouts and update (stage route: stage linearisation, structured solve, back-map, trial
+ * rollouts and update).  BQP_E_ARG before any such loop has run on the handle. */
 int bqp_last_loop_rounds(bqp_handle h, int* rounds);
 
 /* Diagnostic: per instance of the most recent mixed-precision structured solve on this handle

@@ -77,7 +77,8 @@ class LbmpcData(C.Structure):
 
 
 class NmpcDims(C.Structure):
-    _fields_ = [(n, C.c_int) for n in ('N', 'mx', 'mu', 'n_poly')]
+    # subproblem: 0 dense route (the default of a four-argument construction), 1 stage route
+    _fields_ = [(n, C.c_int) for n in ('N', 'mx', 'mu', 'n_poly', 'subproblem')]
 
 
 class NmpcData(C.Structure):
@@ -96,7 +97,7 @@ EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'b
            'bqp_debug_ocp_wpb',
            'bqp_nmpc_linearize', 'bqp_nmpc_linearize_device', 'bqp_nmpc_solve_batched',
            'bqp_nmpc_solve_batched_device', 'bqp_closed_loop_nmpc', 'bqp_closed_loop_nmpc_device',
-           'bqp_last_loop_rounds']
+           'bqp_last_loop_rounds', 'bqp_nmpc_stage_qp', 'bqp_nmpc_stage_qp_device']
 
 _lib = None
 
@@ -171,6 +172,9 @@ def load():
     lib.bqp_nmpc_linearize.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int, C.POINTER(NmpcData)] + \
         [_PD] * 7
     lib.bqp_nmpc_linearize_device.argtypes = lib.bqp_nmpc_linearize.argtypes + [C.c_void_p]
+    lib.bqp_nmpc_stage_qp.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int, C.POINTER(NmpcData)] + \
+        [_PD] * 11
+    lib.bqp_nmpc_stage_qp_device.argtypes = lib.bqp_nmpc_stage_qp.argtypes + [C.c_void_p]
     lib.bqp_nmpc_solve_batched.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int,
                                            C.POINTER(NmpcData), C.POINTER(Options), _PD, _PD, _PD,
                                            _PI, _PI]

@@ -21,6 +21,13 @@ from .loop import ClosedLoop
 from .ocp import OcpResult, _default_handle
 
 _BQP_PLANT_MG_RK4 = 1
+_SUBPROBLEM = {'dense': 0, 'stage': 1}
+
+
+def _subproblem(name):
+    if name not in _SUBPROBLEM:
+        raise ValueError("subproblem is 'dense' or 'stage', not %r" % (name,))
+    return _SUBPROBLEM[name]
 
 
 def _f64(a):
@@ -53,8 +60,8 @@ class NMPC:
                       _f64(F_u.ravel()), _f64(np.asarray(h_u, float).ravel()),
                       _f64(F_T.T), _f64(np.asarray(h_w_N, float).ravel())]
 
-    def _dims(self):
-        return _lib.NmpcDims(self.N, self.mx, self.mu, self.mp)
+    def _dims(self, subproblem='dense'):
+        return _lib.NmpcDims(self.N, self.mx, self.mu, self.mp, _subproblem(subproblem))
 
     def _data(self, x0=None):
         return _lib.NmpcData(*[_lib.ptr(a) for a in self._keep], self.delta,
@@ -83,11 +90,39 @@ class NMPC:
         _lib.check(rc, 'bqp_nmpc_linearize')
         return OcpResult(X=X, cost=cost, c=c, C=np.swapaxes(Ccm, 1, 2), H=H, f=f)
 
-    def solve(self, xmeasure, y0=None, z0=None, handle=None, max_iter=100, tol=1e-8, polish=0):
+    def stage_qp(self, xmeasure, z=None, handle=None):
+        """the stage sub-problem at z as the stage route hands it to the structured solve
+        (bqp_nmpc_stage_qp), in v_k = [dx_k; du_k; dtheta]: A (batch, N, 4, 4), B (batch, N, 4),
+        w (batch, N + 1, 6), xlb / xub (batch, N + 1, 4; stage 0 is -inf / +inf), ulb / uub
+        (batch, N), hp (batch, mp), and the shared W (N + 1, 6, 6) and Fp (mp, 6)."""
+        lib = _lib.load()
+        h = handle or _default_handle()
+        x0 = _f64(np.atleast_2d(xmeasure))
+        b, N, mp = x0.shape[0], self.N, self.mp
+        z = self._z(b, z)
+        Acm = np.zeros((b, N, 4, 4)); B = np.zeros((b, N, 4)); w = np.zeros((b, N + 1, 6))
+        xlb = np.zeros((b, N + 1, 4)); xub = np.zeros((b, N + 1, 4))
+        ulb = np.zeros((b, N)); uub = np.zeros((b, N)); hp = np.zeros((b, mp))
+        W = np.zeros((N + 1, 6, 6)); Fcm = np.zeros((6, mp))
+        dims, dd = self._dims(), self._data(x0)
+        rc = lib.bqp_nmpc_stage_qp(h.value, C.byref(dims), b, C.byref(dd), _lib.ptr(z), _lib.ptr(Acm),
+                                   _lib.ptr(B), _lib.ptr(w), _lib.ptr(xlb), _lib.ptr(xub),
+                                   _lib.ptr(ulb), _lib.ptr(uub), _lib.ptr(hp), _lib.ptr(W),
+                                   _lib.ptr(Fcm))
+        _lib.check(rc, 'bqp_nmpc_stage_qp')
+        return OcpResult(A=np.swapaxes(Acm, 2, 3), B=B, w=w, xlb=xlb, xub=xub, ulb=ulb, uub=uub, hp=hp,
+                         W=np.swapaxes(W, 1, 2), Fp=Fcm.T)
+
+    def solve(self, xmeasure, y0=None, z0=None, handle=None, max_iter=100, tol=1e-8, polish=0,
+              subproblem='dense'):
         """xmeasure (batch, 4) absolute states; y0 a start in the script's layout
         [x_0..x_N; u; theta] (its states are ignored: they follow from u) or z0 = [u - u_eq;
-        theta]; cold start u = u_eq, theta = 0 otherwise.  Returns y_OL (batch, 4 (N + 1) + N + 1)
-        in the script's layout, u0, theta, z, lam (batch, m), cost, exitflag, iterations."""
+        theta]; cold start u = u_eq, theta = 0 otherwise.  subproblem: 'dense' (the condensed
+        sub-problem on the dense kernels) or 'stage' (the sub-problem in stage form on the
+        structured kernel with per-stage models; F_x and F_u must be box rows; polish is then that
+        solve's: 0 / 1 after a 0 / -8 exit, 2 also on weakly active rows, -1 off).  Returns y_OL
+        (batch, 4 (N + 1) + N + 1) in the script's layout, u0, theta, z, lam (batch, m), cost,
+        exitflag, iterations."""
         lib = _lib.load()
         h = handle or _default_handle()
         x0 = _f64(np.atleast_2d(xmeasure))
@@ -98,7 +133,7 @@ class NMPC:
         z = self._z(b, z0)
         lam = np.zeros((b, m)); cost = np.zeros(b)
         flag = np.zeros(b, np.int32); it = np.zeros(b, np.int32)
-        dims, dd = self._dims(), self._data(x0)
+        dims, dd = self._dims(subproblem), self._data(x0)
         o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
         rc = lib.bqp_nmpc_solve_batched(h.value, C.byref(dims), b, C.byref(dd), C.byref(o),
                                         _lib.ptr(z), _lib.ptr(lam), _lib.ptr(cost), _lib.iptr(flag),
@@ -115,12 +150,13 @@ class NMPC:
         return r
 
 
-def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, polish=0):
+def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, polish=0,
+                     subproblem='dense'):
     """Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states x_init
     (batch, 4), absolute: per step the solve at the measured state, the RK4 plant with u_0, and
     the warm start (z shifted one stage, last move repeated, theta kept).  Every instance advances
     at its own step (with BQP_NMPC_SYNC set in the environment: the whole batch step by step, same
-    results).  Returns X (batch, steps + 1, 4), U (batch, steps), exitflag and iterations
+    results).  subproblem as in NMPC.solve.  Returns X (batch, steps + 1, 4), U (batch, steps), exitflag and iterations
     (batch, steps), kernel_ms, launches and rounds, the SQP rounds the loop launched."""
     lib = _lib.load()
     h = handle or _default_handle()
@@ -128,7 +164,7 @@ def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, p
     b, steps = xi.shape[0], int(steps)
     X = np.zeros((b, steps + 1, 4)); U = np.zeros((b, steps))
     fl = np.zeros((b, steps), np.int32); it = np.zeros((b, steps), np.int32)
-    dims, dd = prob._dims(), prob._data()
+    dims, dd = prob._dims(subproblem), prob._data()
     cl = ClosedLoop(_BQP_PLANT_MG_RK4, steps, prob.delta, _lib.ptr(prob.x_eq), _lib.ptr(prob.u_eq))
     o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
     rc = lib.bqp_closed_loop_nmpc(h.value, C.byref(dims), b, C.byref(dd), C.byref(o), C.byref(cl),

@@ -1395,9 +1395,12 @@ static int nmpc_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
         (d->mx > 0 && (!D->F_x || !D->h_x)) || (d->mu > 0 && (!D->F_u || !D->h_u)) ||
         (d->n_poly > 0 && (!D->F_T || !D->h_T)) || (need_x0 && !D->x0))
         return BQP_E_ARG;
+    if (d->subproblem != 0 && d->subproblem != 1) return BQP_E_ARG;
     if (!bqp::nmpc_supported(d->N, d->mx, d->mu)) return BQP_E_UNSUPPORTED;
     const int64_t m = (int64_t)d->N * (d->mx + d->mu) + d->n_poly;
     if (m < 1 || m > 8192) return BQP_E_UNSUPPORTED;
+    // stage route: the terminal rows are the structured kernel's polytope block
+    if (d->subproblem == 1 && bqp::ocp_rpl_for(std::max(d->n_poly, 1)) < 0) return BQP_E_UNSUPPORTED;
     return BQP_OK;
 }
 
@@ -1502,6 +1505,257 @@ static void stage_nmpc_data(Stage& st, const bqp_nmpc_dims* d, const bqp_nmpc_da
     st.in(&Dd->F_T, D->F_T, 5 * mp);    st.in(&Dd->h_T, D->h_T, mp);
 }
 
+// Stage route (bqp_nmpc_dims.subproblem = 1): the SQP's kernel arguments over the handle's nwork
+// in its NworkStage layout, and the structured solve's call over the same arrays - per-stage models
+// A_k, B_k (c = 0), the shared W and Fp, per-instance w, bounds and hp, x0 = 0, skip = done, duals
+// requested.  The caller's A .. Fp (the diagnostic entry's outputs) replace the workspace's where
+// non-null.
+struct NmpcStageRoute {
+    bqp::NmpcArgs a;
+    bqp::NmpcStageArgs s;
+    bqp_ocp_dims od;
+    bqp_ocp_data oD;
+    bqp_ocp_duals du;
+    bqp_options qo;
+    double *xo, *uo, *tho, *fv;
+    int* sflag;
+};
+
+static int nmpc_stage_setup(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                            const bqp_options& o, hipStream_t st, NmpcStageRoute& R,
+                            const bqp::NmpcStageArgs* user = nullptr) {
+    const int N = d->N, n = N + 1, mp = d->n_poly, m = N * (d->mx + d->mu) + mp;
+    const size_t B = batch;
+    const layout::NworkStage NL(batch, N, mp, m, LB_NTRIAL, sizeof(bqp::NmpcBoundMap));
+    if (getenv("BQP_LB_TRACE"))
+        fprintf(stderr, "bqp nmpc stage route: workspace %zu bytes for %d instances\n", NL.bytes, batch);
+    HIP_TRY(h->nwork.reserve(NL.bytes));
+    void* nw = h->nwork.p;
+    bqp::NmpcArgs& a = R.a;
+    memset(&a, 0, sizeof(a));
+    a.N = N; a.n = n; a.nr = 5 * N + 8; a.m = m; a.mx = d->mx; a.mu = d->mu; a.mp = mp;
+    a.batch = batch; a.ntrial = LB_NTRIAL; a.max_iter = o.max_iter;
+    a.delta = D->delta;
+    a.tol_step = o.tol_stat;            // as the dense route
+    a.tol_stat = 10.0 * o.tol_stat;
+    a.Lq = D->Lq; a.Lr = D->Lr; a.Lp = D->Lp; a.Lt = D->Lt; a.LAM = D->LAMBDA; a.PSI = D->PSI;
+    a.xeq = D->x_eq; a.ueq = D->u_eq; a.Fx = D->F_x; a.hx = D->h_x; a.Fu = D->F_u; a.hu = D->h_u;
+    a.FT = D->F_T; a.hT = D->h_T;
+    a.x0 = D->x0; a.sx0 = D->sx0;
+    a.f = layout::at<double>(nw, NL.f);
+    a.ctl = layout::at<double>(nw, NL.ctl);
+    a.rhs = layout::at<double>(nw, NL.rhs);
+    a.lam = layout::at<double>(nw, NL.lam);
+    a.d = layout::at<double>(nw, NL.d);
+    a.cost0 = layout::at<double>(nw, NL.cost0);
+    a.costT = layout::at<double>(nw, NL.costT);
+    a.violT = layout::at<double>(nw, NL.violT);
+    a.stat = layout::at<double>(nw, NL.stat);
+    a.cprev = layout::at<double>(nw, NL.cprev);
+    a.nu = layout::at<double>(nw, NL.nu);
+    a.qpflag = layout::at<int>(nw, NL.qpflag);
+    a.done = layout::at<int>(nw, NL.done);
+    a.ndone = layout::at<int>(nw, NL.ndone);
+    HIP_TRY(hipMemsetAsync(a.done, 0, sizeof(int) * (B + 1), st));   // done[], ndone
+    HIP_TRY(hipMemsetAsync(a.nu, 0, sizeof(double) * B, st));
+    bqp::NmpcStageArgs& s = R.s;
+    memset(&s, 0, sizeof(s));
+    auto pick = [&](double* u, const layout::Region& r) { return u ? u : layout::at<double>(nw, r); };
+    s.A = pick(user ? user->A : nullptr, NL.A);
+    s.B = pick(user ? user->B : nullptr, NL.B);
+    s.w = pick(user ? user->w : nullptr, NL.w);
+    s.xlb = pick(user ? user->xlb : nullptr, NL.xlb);
+    s.xub = pick(user ? user->xub : nullptr, NL.xub);
+    s.ulb = pick(user ? user->ulb : nullptr, NL.ulb);
+    s.uub = pick(user ? user->uub : nullptr, NL.uub);
+    s.hp = pick(user ? user->hp : nullptr, NL.hp);
+    s.W = pick(user ? user->W : nullptr, NL.W);
+    s.Fp = pick(user ? user->Fp : nullptr, NL.Fp);
+    s.map = layout::at<bqp::NmpcBoundMap>(nw, NL.map);
+    R.xo = layout::at<double>(nw, NL.xo);
+    R.uo = layout::at<double>(nw, NL.uo);
+    R.tho = layout::at<double>(nw, NL.tho);
+    R.fv = layout::at<double>(nw, NL.fv);
+    R.sflag = layout::at<int>(nw, NL.sflag);
+    R.du.pi = nullptr;
+    R.du.lam_x = layout::at<double>(nw, NL.lamx);
+    R.du.lam_u = layout::at<double>(nw, NL.lamu);
+    R.du.lam_p = layout::at<double>(nw, NL.lamp);
+    s.uo = R.uo; s.tho = R.tho; s.lamx = R.du.lam_x; s.lamu = R.du.lam_u; s.lamp = R.du.lam_p;
+    s.sflag = R.sflag;
+    double* x0z = layout::at<double>(nw, NL.x0z);
+    HIP_TRY(hipMemsetAsync(x0z, 0, sizeof(double) * 4, st));
+    // the shared tables and the bound map; one flag back: F_x, F_u must be box rows
+    HIP_TRY(bqp::launch_nmpc_stage_table(a, s, st));
+    int notbox = 0;
+    HIP_TRY(hipMemcpyAsync(&notbox, &s.map->notbox, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (notbox) return BQP_E_UNSUPPORTED;
+    memset(&R.od, 0, sizeof(R.od));
+    R.od.nx = 4; R.od.nu = 1; R.od.np = 1; R.od.N = N; R.od.n_poly = mp; R.od.poly_stage = N;
+    R.od.stage_models = 1;
+    bqp_ocp_data& oD = R.oD;
+    memset(&oD, 0, sizeof(oD));
+    oD.A = s.A; oD.sA = 16 * (int64_t)N;
+    oD.B = s.B; oD.sB = 4 * (int64_t)N;
+    oD.c = nullptr;
+    oD.W = s.W; oD.sW = 0;
+    oD.w = s.w; oD.sw = 6 * (int64_t)(N + 1);
+    oD.xlb = s.xlb; oD.xub = s.xub; oD.sxb = 4 * (int64_t)(N + 1);
+    oD.ulb = s.ulb; oD.uub = s.uub; oD.sub = N;
+    oD.Fp = mp > 0 ? s.Fp : nullptr; oD.sFp = 0;
+    oD.hp = mp > 0 ? s.hp : nullptr; oD.shp = mp;
+    oD.x0 = x0z; oD.sx0 = 0;
+    oD.skip = a.done;
+    // the sub-problem's options: the structured solve's defaults with the dense sub-problem's
+    // iteration limit; polish as the caller set it, in that solve's own encoding
+    bqp_default_options(&R.qo);
+    R.qo.max_iter = 100;
+    R.qo.polish = o.polish;
+    return BQP_OK;
+}
+
+// one SQP round of the stage route: stage linearisation, structured solve (+ its repair launch),
+// back-map, trial rollouts, update.  The structured call records the handle's own events and
+// launch count; the callers keep theirs.  ev (may be null): 6 events around the 5 phases
+static int nmpc_stage_round(bqp_handle h, const NmpcStageRoute& R, hipStream_t st, int* launches,
+                            EventGuard* ev = nullptr) {
+    auto mark = [&](int k) -> int {
+        if (!ev) return BQP_OK;
+        if (!ev[k].e) HIP_TRY(hipEventCreate(&ev[k].e));
+        HIP_TRY(hipEventRecord(ev[k].e, st));
+        return BQP_OK;
+    };
+    BQP_TRY(mark(0));
+    HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st));
+    BQP_TRY(mark(1));
+    BQP_TRY(bqp_solve_ocp_batched_device(h, &R.od, R.a.batch, &R.oD, &R.qo, R.xo, R.uo, R.tho, R.fv, R.sflag,
+                                         nullptr, &R.du, st));
+    *launches += h->launches;
+    BQP_TRY(mark(2));
+    HIP_TRY(bqp::launch_nmpc_stage_backmap(R.a, R.s, st));
+    BQP_TRY(mark(3));
+    HIP_TRY(bqp::launch_nmpc_rollout(R.a, 0, st));
+    BQP_TRY(mark(4));
+    HIP_TRY(bqp::launch_nmpc_update(R.a, st));
+    BQP_TRY(mark(5));
+    *launches += 4;
+    return BQP_OK;
+}
+
+// the stage route's form of bqp_nmpc_solve_batched_device (arguments checked there)
+static int nmpc_solve_stage(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                            const bqp_options& o, double* z, double* lam, double* cost, int* exitflag,
+                            int* iterations, hipStream_t st) {
+    const size_t B = batch;
+    NmpcStageRoute R;
+    BQP_TRY(nmpc_stage_setup(h, d, batch, D, o, st, R));
+    bqp::NmpcArgs& a = R.a;
+    a.z = z; a.flag = exitflag; a.iters = iterations;
+    if (lam) a.lam = lam;
+    HIP_TRY(hipMemsetAsync(a.iters, 0, sizeof(int) * B, st));
+    HIP_TRY(hipMemsetAsync(a.flag, 0, sizeof(int) * B, st));
+    // the structured call records h->ev0 / ev1 for itself: this solve's start is an event of its own
+    EventGuard e0;
+    HIP_TRY(hipEventCreate(&e0.e));
+    HIP_TRY(hipEventRecord(e0.e, st));
+    int launches = 1;                    // the table launch
+    h->nmpc_rounds = 0;
+    // BQP_LB_TRACE as on the dense route: 1 the sub-problems' exit flags, 2 per-launch event times
+    const char* tenv = getenv("BQP_LB_TRACE");
+    const bool trace = tenv && atoi(tenv) >= 2, trace_flags = tenv && !trace;
+    EventGuard ev[6];
+    for (int it = 0; it < o.max_iter; ++it) {
+        BQP_TRY(nmpc_stage_round(h, R, st, &launches, trace ? ev : nullptr));
+        ++h->nmpc_rounds;
+        if (trace) {
+            HIP_TRY(hipEventSynchronize(ev[5].e));
+            float ms[5];
+            for (int j = 0; j < 5; ++j) HIP_TRY(hipEventElapsedTime(&ms[j], ev[j].e, ev[j + 1].e));
+            fprintf(stderr, "bqp nmpc it %d ms: stage-linearise %.3f structured(+repair) %.3f back-map %.3f trials %.3f update %.3f\n",
+                    it, ms[0], ms[1], ms[2], ms[3], ms[4]);
+        }
+        if (trace_flags) {
+            std::vector<int> fl(B), dn(B);
+            HIP_TRY(hipMemcpyAsync(fl.data(), R.sflag, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipMemcpyAsync(dn.data(), a.done, sizeof(int) * B, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            // (done as of the end of the round: an instance that stopped in it is still listed)
+            for (size_t b = 0; b < B; ++b)
+                fprintf(stderr, "bqp nmpc it %d instance %zu: stage sub-problem flag %d%s\n", it, b, fl[b],
+                        dn[b] ? " (stopped)" : "");
+        }
+        if ((it + 1) % (a.n >= 64 ? 1 : 4) == 0 || it + 1 == o.max_iter) {
+            int nd_h = 0;
+            HIP_TRY(hipMemcpyAsync(&nd_h, a.ndone, sizeof(int), hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (nd_h >= batch) break;
+        }
+    }
+    HIP_TRY(hipEventRecord(h->ev1, st));
+    std::swap(h->ev0, e0.e);   // the guard destroys the previous start event
+    h->timed = true;
+    h->launches = launches;
+    if (cost) HIP_TRY(hipMemcpyAsync(cost, a.cost0, sizeof(double) * B, hipMemcpyDeviceToDevice, st));
+    return BQP_OK;
+}
+
+int bqp_nmpc_stage_qp_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                             const bqp_nmpc_data* D, const double* z, double* A, double* B,
+                             double* w, double* xlb, double* xub, double* ulb, double* uub,
+                             double* hp, double* W, double* Fp, void* stream) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z) return BQP_E_ARG;
+    if (bqp::ocp_rpl_for(std::max(d->n_poly, 1)) < 0) return BQP_E_UNSUPPORTED;
+    DevScope ds(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    bqp_options o;
+    resolve(nullptr, &o);
+    bqp::NmpcStageArgs user;
+    memset(&user, 0, sizeof(user));
+    user.A = A; user.B = B; user.w = w; user.xlb = xlb; user.xub = xub; user.ulb = ulb; user.uub = uub;
+    user.hp = hp; user.W = W; user.Fp = Fp;
+    NmpcStageRoute R;
+    BQP_TRY(nmpc_stage_setup(h, d, batch, D, o, st, R, &user));
+    R.a.z = const_cast<double*>(z);     // read only by the rollout
+    HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st));
+    return BQP_OK;
+}
+
+int bqp_nmpc_stage_qp(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                      const double* z, double* A, double* B, double* w, double* xlb, double* xub,
+                      double* ulb, double* uub, double* hp, double* W, double* Fp) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z) return BQP_E_ARG;
+    DevScope ds(h->device);
+    const size_t Bt = batch, N = d->N, mp = d->n_poly;
+    Stage st(h);
+    bqp_nmpc_data Dd;
+    const double* zd;
+    double *Ad = nullptr, *Bd = nullptr, *wd = nullptr, *xld = nullptr, *xud = nullptr, *uld = nullptr,
+           *uud = nullptr, *hpd = nullptr, *Wd = nullptr, *Fpd = nullptr;
+    stage_nmpc_data(st, d, D, &Dd);
+    st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
+    st.in(&zd, z, Bt * (N + 1));
+    if (A) st.out(&Ad, Bt * N * 16, A);
+    if (B) st.out(&Bd, Bt * N * 4, B);
+    if (w) st.out(&wd, Bt * (N + 1) * 6, w);
+    if (xlb) st.out(&xld, Bt * (N + 1) * 4, xlb);
+    if (xub) st.out(&xud, Bt * (N + 1) * 4, xub);
+    if (ulb) st.out(&uld, Bt * N, ulb);
+    if (uub) st.out(&uud, Bt * N, uub);
+    if (hp && mp) st.out(&hpd, Bt * mp, hp);
+    if (W) st.out(&Wd, (N + 1) * 36, W);
+    if (Fp && mp) st.out(&Fpd, mp * 6, Fp);
+    BQP_TRY(st.commit());
+    BQP_TRY(bqp_nmpc_stage_qp_device(h, d, batch, &Dd, zd, Ad, Bd, wd, xld, xud, uld, uud, hpd, Wd, Fpd,
+                                     h->stream));
+    return st.finish();
+}
+
+
 int bqp_nmpc_linearize(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
                        const double* z, double* X, double* cost, double* c, double* C, double* H,
                        double* f) {
@@ -1539,6 +1793,7 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
     hipStream_t st = (hipStream_t)stream;
     bqp_options o;
     resolve(opt, &o);
+    if (d->subproblem == 1) return nmpc_solve_stage(h, d, batch, D, o, z, lam, cost, exitflag, iterations, st);
     const size_t B = batch;
     bqp::NmpcArgs a;
     bqp::LbmpcArgs ne;
@@ -1700,10 +1955,18 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
         Dl.sx0 = 4;
         bqp_options o;
         resolve(opt, &o);
-        bqp::NmpcArgs a;
+        const bool stage = d->subproblem == 1;
+        NmpcStageRoute R;
+        bqp::NmpcArgs ad;
         bqp::LbmpcArgs ne;
         bqp::DenseKernelArgs q;
-        HIP_TRY(nmpc_setup(h, d, batch, &Dl, o, nullptr, nullptr, nullptr, st, a, ne, &q));
+        if (stage) {
+            BQP_TRY(nmpc_stage_setup(h, d, batch, &Dl, o, st, R));
+            launches += 1;               // the table launch
+        } else {
+            HIP_TRY(nmpc_setup(h, d, batch, &Dl, o, nullptr, nullptr, nullptr, st, ad, ne, &q));
+        }
+        bqp::NmpcArgs& a = stage ? R.a : ad;
         a.z = z; ne.z = z; a.flag = fl; a.iters = it;
         HIP_TRY(hipMemsetAsync(it, 0, sizeof(int) * B, st));
         HIP_TRY(hipMemsetAsync(fl, 0, sizeof(int) * B, st));
@@ -1722,13 +1985,18 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
         // an instance stops within max_iter rounds of its step's first: the bound is never reached
         const int64_t max_rounds = (int64_t)S * o.max_iter;
         for (int64_t r = 0; r < max_rounds; ++r) {
-            HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st));
-            HIP_TRY(bqp::launch_lbmpc_normal(ne, st));
-            HIP_TRY(bqp::launch_dense(q, st));
-            HIP_TRY(bqp::launch_nmpc_rollout(a, 0, st));
-            HIP_TRY(bqp::launch_nmpc_update(a, st));
+            if (stage) {
+                BQP_TRY(nmpc_stage_round(h, R, st, &launches));
+            } else {
+                HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st));
+                HIP_TRY(bqp::launch_lbmpc_normal(ne, st));
+                HIP_TRY(bqp::launch_dense(q, st));
+                HIP_TRY(bqp::launch_nmpc_rollout(a, 0, st));
+                HIP_TRY(bqp::launch_nmpc_update(a, st));
+                launches += 5;
+            }
             HIP_TRY(bqp::launch_nmpc_loop_advance(v, st));
-            launches += 6;
+            launches += 1;
             ++rounds;
             int nf = 0;
             HIP_TRY(hipMemcpyAsync(&nf, nfin, sizeof(int), hipMemcpyDeviceToHost, st));

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "bqp_nmpc_advance.h"
+#include "bqp_nmpc_stage.h"
 #include "bqp_track.h"
 
 namespace bqp {
@@ -182,8 +183,25 @@ struct NmpcArgs {
     double *stat, *cprev, *nu;          // batch each; nu: the merit function's penalty
     double *Xout, *cout;                // linearisation only (may be null): rollout, c
     int *qpflag, *flag, *done, *iters, *ndone;
+    double* ctl;                        // stage route: batch x n, C'lam ready-made (C is null)
+};
+static_assert(NMS_MAXMX == NMPC_MAXMX && NMS_MAXMU == NMPC_MAXMU, "bqp_nmpc_stage.h's row limits");
+// Stage route (bqp_nmpc_dims.subproblem = 1): the stage problem of the structured solve and that
+// solve's outputs, per instance unless said (strides: bqp_layout.h NworkStage)
+struct NmpcStageArgs {
+    double *A, *B, *w, *xlb, *xub, *ulb, *uub, *hp;   // 16 N, 4 N, 6 (N+1), 4 (N+1) x 2, N x 2, mp
+    double *W, *Fp;                                  // shared: 36 (N+1), 6 mp column-major
+    NmpcBoundMap* map;                               // shared
+    const double *uo, *tho, *lamx, *lamu, *lamp;     // the solve's u, theta and multipliers
+    const int* sflag;                                // and exit flags
 };
 bool nmpc_supported(int N, int mx, int mu);
+// stage route: the shared tables (W, Fp, bound map), once per solve
+hipError_t launch_nmpc_stage_table(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st);
+// the rollout at z with the stage Jacobians: A, B, w, bounds, hp, rhs, cost0
+hipError_t launch_nmpc_stage_rollout(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st);
+// after the structured solve: d, lam in NMPC row order, qpflag, f and C'lam by the adjoint sweep
+hipError_t launch_nmpc_stage_backmap(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st);
 // gn = 1: rollout with sensitivities at z (Jr, er, C, rhs, cost0); gn = 0: the ntrial trial points
 hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st);
 hipError_t launch_nmpc_update(const NmpcArgs& a, hipStream_t st);

@@ -131,6 +131,57 @@ struct Nwork : Arena {
     }
 };
 
+// nwork on the stage route (bqp_nmpc_dims.subproblem = 1): no Jr, H or C.  Per instance the stage
+// problem the structured solve reads (A 16 N, B 4 N, w 6 (N+1), bounds, hp), that solve's outputs
+// (x, u, theta, fval, lam_x, lam_u, lam_p, exit flag), the SQP's vectors as Nwork has them, and
+// the back-map's f and C'lam (n each); shared by the batch the cost blocks W (36 (N+1)), the
+// polytope matrix Fp (6 mp), the zero initial state and the bound map (map_bytes, 8-aligned).
+// 79 KB per instance at N = 100 with the 616-row terminal set, against Nwork's 1.8 MB.
+// ndone follows done directly: one memset zeroes both
+struct NworkStage : Arena {
+    size_t n;
+    Region A, B, w, xlb, xub, ulb, uub, hp, xo, uo, tho, fv, lamx, lamu, lamp;
+    Region rhs, lam, d, f, ctl, cost0, costT, violT, stat, cprev, nu;
+    Region W, Fp, x0z, map;
+    Region sflag, qpflag, done, ndone;
+    NworkStage(size_t Bt, size_t N, size_t mp, size_t m, size_t ntrial, size_t map_bytes) : n(N + 1) {
+        A = take<double>(Bt * N * 16);
+        B = take<double>(Bt * N * 4);
+        w = take<double>(Bt * (N + 1) * 6);
+        xlb = take<double>(Bt * (N + 1) * 4);
+        xub = take<double>(Bt * (N + 1) * 4);
+        ulb = take<double>(Bt * N);
+        uub = take<double>(Bt * N);
+        hp = take<double>(Bt * mp);
+        xo = take<double>(Bt * (N + 1) * 4);
+        uo = take<double>(Bt * N);
+        tho = take<double>(Bt);
+        fv = take<double>(Bt);
+        lamx = take<double>(Bt * (N + 1) * 8);
+        lamu = take<double>(Bt * N * 2);
+        lamp = take<double>(Bt * mp);
+        rhs = take<double>(Bt * m);
+        lam = take<double>(Bt * m);
+        d = take<double>(Bt * n);
+        f = take<double>(Bt * n);
+        ctl = take<double>(Bt * n);
+        cost0 = take<double>(Bt);
+        costT = take<double>(Bt * ntrial);
+        violT = take<double>(Bt * ntrial);
+        stat = take<double>(Bt);
+        cprev = take<double>(Bt);
+        nu = take<double>(Bt);
+        W = take<double>((N + 1) * 36);
+        Fp = take<double>(mp * 6);
+        x0z = take<double>(4);
+        map = take_aligned(map_bytes, alignof(double));
+        sflag = take<int>(Bt);
+        qpflag = take<int>(Bt);
+        done = take<int>(Bt);
+        ndone = take<int>(1);
+    }
+};
+
 // dwork: the dense kernel's scratch (work_doubles per instance) and its stats
 struct Dwork : Arena {
     Region scratch, stats;

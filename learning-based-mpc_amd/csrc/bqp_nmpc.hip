@@ -21,6 +21,16 @@
 //                               matrix cores, f = 2 Jr'e
 //   nmpc_update_kernel          one wave per instance: stationarity |f + C'lam| over the
 //                               instance's C, penalty, L1 merit line search, z += alpha d
+//                               (<true>: from the back-map's ready C'lam)
+// Stage route (bqp_nmpc_dims.subproblem = 1) = stage rollout -> structured solve with per-stage
+// models (bqp_ocp.hip) -> back-map -> rollout(trials) -> update<true>; no Jr, H or C:
+//   nmpc_stage_table_kernel     once per solve: the shared cost blocks W, the polytope matrix Fp,
+//                               the bound map of F_x / F_u and its "not a box" flag
+//   nmpc_stage_rollout_kernel   one wave per instance: the rollout of <true> without
+//                               sensitivities; A_k, B_k, the stage gradients w_k, the rows as
+//                               bounds on dx_k, du_k, hp, rhs = -c, cost
+//   nmpc_stage_backmap_kernel   one wave per instance: d, lam in NMPC row order, the sub-problem's
+//                               flag, f and C'lam by one adjoint sweep over A_k, B_k
 //   nmpc_loop_shift_kernel      step-synchronous closed loop: the warm start of the next step
 //   nmpc_loop_advance_kernel    asynchronous closed loop, after every iteration: the instances
 //                               whose SQP has stopped move to their next closed-loop step
@@ -118,22 +128,9 @@ constexpr int NO_Q = 0, NO_R = NO_Q + 16, NO_P = NO_R + 1, NO_T = NO_P + 16, NO_
               NO_HX = NO_FX + 4 * NMPC_MAXMX, NO_FU = NO_HX + NMPC_MAXMX, NO_HU = NO_FU + NMPC_MAXMU,
               NO_END = NO_HU + NMPC_MAXMU;
 
-template <bool GN>
-__global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a) {
-    const int lane = threadIdx.x;
-    const int nt = GN ? 1 : a.ntrial;
-    const int b = blockIdx.x / nt, t = blockIdx.x % nt;
-    if (b >= a.batch || a.done[b]) return;
-    const int N = a.N, n = a.n, m = a.m, mx = a.mx, mu = a.mu, ms = mx + mu, mp = a.mp;
-    __shared__ double zsh[NM_WAVE * NM_CPL];
-    __shared__ double cst[NO_END];
-    __shared__ double SNs[GN ? 4 * NM_WAVE * NM_CPL : 1];   // S_N, row c at SNs[128 c ..]
-    {
-        const double alpha = GN ? 0.0 : ldexp(1.0, -t);
-        const double* z = a.z + (int64_t)b * n;
-        const double* dz = a.d + (int64_t)b * n;
-        for (int j = lane; j < n; j += NM_WAVE) zsh[j] = GN ? z[j] : z[j] + alpha * dz[j];
-    }
+// the constant block into LDS, lanes over its entries (the caller syncs the wave)
+__device__ __forceinline__ void nm_load_consts(const NmpcArgs& a, int lane, double* cst) {
+    const int mx = a.mx, mu = a.mu;
     for (int i = lane; i < NO_END; i += NM_WAVE) {
         double v = 0.0;
         if (i < NO_R) v = a.Lq[i - NO_Q];
@@ -150,6 +147,25 @@ __global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a) {
         else { const int e = i - NO_HU; if (e < mu) v = a.hu[e]; }
         cst[i] = v;
     }
+}
+
+template <bool GN>
+__global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a) {
+    const int lane = threadIdx.x;
+    const int nt = GN ? 1 : a.ntrial;
+    const int b = blockIdx.x / nt, t = blockIdx.x % nt;
+    if (b >= a.batch || a.done[b]) return;
+    const int N = a.N, n = a.n, m = a.m, mx = a.mx, mu = a.mu, ms = mx + mu, mp = a.mp;
+    __shared__ double zsh[NM_WAVE * NM_CPL];
+    __shared__ double cst[NO_END];
+    __shared__ double SNs[GN ? 4 * NM_WAVE * NM_CPL : 1];   // S_N, row c at SNs[128 c ..]
+    {
+        const double alpha = GN ? 0.0 : ldexp(1.0, -t);
+        const double* z = a.z + (int64_t)b * n;
+        const double* dz = a.d + (int64_t)b * n;
+        for (int j = lane; j < n; j += NM_WAVE) zsh[j] = GN ? z[j] : z[j] + alpha * dz[j];
+    }
+    nm_load_consts(a, lane, cst);
     wave_sync();
     const double th = zsh[N];
     const double ueq = cst[NO_UE], psi = cst[NO_PSI];
@@ -343,6 +359,8 @@ __global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a) {
 // ------------------------------------------------------------------------------------------
 // convergence test + penalty + L1 merit line search + step (one wave per instance)
 // ------------------------------------------------------------------------------------------
+// STAGE: C'lam is the back-map's ready n-vector a.ctl (stage route), not the product over C
+template <bool STAGE>
 __global__ void __launch_bounds__(64) nmpc_update_kernel(NmpcArgs a) {
     const int b = blockIdx.x;
     const int lane = threadIdx.x;
@@ -353,13 +371,16 @@ __global__ void __launch_bounds__(64) nmpc_update_kernel(NmpcArgs a) {
     const double* f = a.f + (int64_t)b * n;
     const double* lam = a.lam + (int64_t)b * m;
     const double* rhs = a.rhs + (int64_t)b * m;
-    const double* C = a.C + (int64_t)b * m * n;
+    const double* C = STAGE ? nullptr : a.C + (int64_t)b * m * n;
     const int qflag = a.qpflag[b];
     double st = 0.0, fn = 0.0, dn = 0.0, zn = 0.0, sl = 0.0, viol = -INFINITY, V0 = 0.0, lmax = 0.0;
     // C'lam by groups of 16 columns: lanes over the rows (coalesced loads, 16 in flight), one
     // transposed wave sum per group - the pattern of lbmpc_update_kernel over the instance's own C
     __shared__ double sg[NM_WAVE * NM_CPL];
-    for (int g0 = 0; g0 < n; g0 += 16) {
+    if (STAGE) {
+        for (int j = lane; j < n; j += NM_WAVE) sg[j] = a.ctl[(int64_t)b * n + j];
+    }
+    for (int g0 = 0; !STAGE && g0 < n; g0 += 16) {
         double ac[16];
 #pragma unroll
         for (int c = 0; c < 16; ++c) ac[c] = 0.0;
@@ -496,8 +517,348 @@ __global__ void __launch_bounds__(64) nmpc_loop_advance_kernel(NmpcAdvanceArgs a
 }
 
 // ------------------------------------------------------------------------------------------
+// stage route (bqp_nmpc_dims.subproblem = 1): the sub-problem stays in stage form,
+//   v_k = [dx_k; du_k; dtheta],  dx_0 = 0,  dx_{k+1} = A_k dx_k + B_k du_k,
+//   cost sum 0.5 v_k'W_k v_k + w_k'v_k,  bounds on dx_k (k = 1..N) and du_k, F_T rows at stage N,
+// and is solved by the structured kernel with per-stage models (bqp_ocp.hip).  Condensed, it is
+// the dense route's H, f, C, c (tests/nmpc_stage_ref.py).
+// ------------------------------------------------------------------------------------------
+// entry (r, c) of the 6 x 6 cost block in v = [x (4); u; theta]: running
+//   2 (Mx'(delta Q) Mx + Mu'(delta R) Mu),  Mx = [I 0 -LAMBDA], Mu = [0 1 -PSI]
+// or terminal 2 (Mx' P Mx + Mt' T Mt), Mt = [0 0 LAMBDA]; L'L = delta Q (or P), factors row-major
+__device__ inline double nm_wentry(const double* L, const double* Lt, double lr, const double* LAM,
+                                   double psi, bool term, int r, int c) {
+    auto gram = [&](const double* F, int i, int j) {      // (F'F)[i][j]
+        double v = 0.0;
+        for (int q = 0; q < 4; ++q) v += F[4 * q + i] * F[4 * q + j];
+        return v;
+    };
+    auto gl = [&](const double* F, int i) {               // (F'F LAMBDA)[i]
+        double v = 0.0;
+        for (int j = 0; j < 4; ++j) v += gram(F, i, j) * LAM[j];
+        return v;
+    };
+    auto lgl = [&](const double* F) {                     // LAMBDA'F'F LAMBDA
+        double v = 0.0;
+        for (int i = 0; i < 4; ++i) v += LAM[i] * gl(F, i);
+        return v;
+    };
+    const double R = lr * lr;
+    if (r > c) { const int t = r; r = c; c = t; }
+    if (c < 4) return 2.0 * gram(L, r, c);
+    if (r < 4) return c == 4 ? 0.0 : -2.0 * gl(L, r);
+    if (term) return (r == 5 && c == 5) ? 2.0 * (lgl(L) + lgl(Lt)) : 0.0;
+    if (r == 4) return c == 4 ? 2.0 * R : -2.0 * R * psi;
+    return 2.0 * (lgl(L) + psi * psi * R);
+}
+
+// once per solve: the shared cost blocks W ((N + 1) x 36), the polytope matrix
+// Fp = [F_T[:, :4] | 0 | F_T[:, 4]] (mp x 6, column-major) and the bound map of F_x, F_u with its
+// "not a box" flag
+__global__ void __launch_bounds__(64) nmpc_stage_table_kernel(NmpcArgs a, NmpcStageArgs s) {
+    const int lane = threadIdx.x, N = a.N, mp = a.mp;
+    for (int i = lane; i < 36 * (N + 1); i += NM_WAVE) {
+        const int blk = i / 36, e = i % 36;
+        const bool term = blk == N;
+        s.W[i] = nm_wentry(term ? a.Lp : a.Lq, a.Lt, a.Lr[0], a.LAM, a.PSI[0], term, e % 6, e / 6);
+    }
+    for (int i = lane; i < 6 * mp; i += NM_WAVE) {
+        const int c = i / mp, r = i % mp;
+        s.Fp[i] = c < 4 ? a.FT[r + (int64_t)mp * c] : (c == 4 ? 0.0 : a.FT[r + (int64_t)mp * 4]);
+    }
+    if (lane == 0) nmpc_bound_map_build(a.Fx, a.mx, a.Fu, a.mu, s.map);
+}
+
+// the bound map into LDS, lanes over its words (the caller syncs the wave)
+__device__ __forceinline__ void nm_load_map(const NmpcBoundMap* g, int lane, NmpcBoundMap* l) {
+    static_assert(sizeof(NmpcBoundMap) % sizeof(int) == 0, "copied by ints");
+    for (int i = lane; i < (int)(sizeof(NmpcBoundMap) / sizeof(int)); i += NM_WAVE)
+        ((int*)l)[i] = ((const int*)g)[i];
+}
+
+// The third mode of the rollout, one wave per instance: nm_rk4<true> from the measured state
+// without sensitivities - the rollout and the stage Jacobians are the operation sequence of
+// nmpc_rollout_kernel<true>.  Every lane carries the rollout (the work per stage is wave-uniform);
+// lanes 0..25 store the stage's A_k | B_k | w_k, lanes i < mx + mu the value of row i of the next
+// stage (rhs = -c) and the bound it stands for, lanes over the rows of F_T the terminal rhs and hp.
+__global__ void __launch_bounds__(64) nmpc_stage_rollout_kernel(NmpcArgs a, NmpcStageArgs s) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    if (b >= a.batch || a.done[b]) return;
+    const int N = a.N, n = a.n, m = a.m, mx = a.mx, mu = a.mu, ms = mx + mu, mp = a.mp;
+    __shared__ double zsh[NM_WAVE * NM_CPL];
+    __shared__ double cst[NO_END];
+    __shared__ NmpcBoundMap map;
+    {
+        const double* z = a.z + (int64_t)b * n;
+        for (int j = lane; j < n; j += NM_WAVE) zsh[j] = z[j];
+    }
+    nm_load_consts(a, lane, cst);
+    nm_load_map(s.map, lane, &map);
+    wave_sync();
+    const double th = zsh[N];
+    const double ueq = cst[NO_UE], psi = cst[NO_PSI];
+    double x[4];
+    {
+        const double* x0 = a.x0 + (int64_t)b * a.sx0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = x0[i];
+    }
+    double* xlb = s.xlb + (int64_t)b * (N + 1) * 4;
+    double* xub = s.xub + (int64_t)b * (N + 1) * 4;
+    double* ulb = s.ulb + (int64_t)b * N;
+    double* uub = s.uub + (int64_t)b * N;
+    double* rhs = a.rhs + (int64_t)b * m;
+    // the bounds no row stands for (stage 0 of the state bounds is not read by the solve)
+    for (int i = lane; i < 4 * (N + 1); i += NM_WAVE) {
+        if (i < 4 || map.rowof[i & 3][0] < 0) xlb[i] = -INFINITY;
+        if (i < 4 || map.rowof[i & 3][1] < 0) xub[i] = INFINITY;
+    }
+    for (int i = lane; i < N; i += NM_WAVE) {
+        if (map.rowof[4][0] < 0) ulb[i] = -INFINITY;
+        if (map.rowof[4][1] < 0) uub[i] = INFINITY;
+    }
+    // the lane's slot in the stage record [A_k (16, column-major) | B_k (4) | w_k (6)]
+    double* rec = nullptr;
+    int rstride = 0;
+    if (lane < 16) { rec = s.A + (int64_t)b * N * 16 + lane; rstride = 16; }
+    else if (lane < 20) { rec = s.B + (int64_t)b * N * 4 + (lane - 16); rstride = 4; }
+    else if (lane < 26) { rec = s.w + (int64_t)b * (N + 1) * 6 + (lane - 20); rstride = 6; }
+    // the lane's row of [F_x; F_u] as a bound: array and stride over the stages
+    double* bnd = nullptr;
+    int bstride = 0;
+    if (lane < ms) {
+        const bool isx = nmpc_row_is_state(mx, lane);
+        bnd = (isx ? (map.side[lane] ? xub : xlb) : (map.side[lane] ? uub : ulb)) + nmpc_bound_index(map, mx, 1, lane);
+        bstride = isx ? 4 : 1;
+    }
+    double J = 0.0;
+    // weighted residual e = L (xx - x_eq - LAMBDA theta) as nmpc_rollout_kernel's xresidual forms
+    // it, and the x block of the stage gradient 2 L'e
+    auto xgrad = [&](int oL, const double (&xx)[4], double (&wx)[4]) __attribute__((always_inline)) {
+        double e[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double er = 0.0;
+#pragma unroll
+            for (int c2 = r; c2 < 4; ++c2) er += cst[oL + 4 * r + c2] * (xx[c2] - cst[NO_XE + c2] - cst[NO_L + c2] * th);
+            J += er * er;
+            e[r] = er;
+        }
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) {
+            double v = 0.0;
+#pragma unroll
+            for (int r = 0; r <= c2; ++r) v += cst[oL + 4 * r + c2] * e[r];
+            wx[c2] = 2.0 * v;
+        }
+    };
+    // theta entry of the stage gradient from its x and u entries: -LAMBDA'wx - PSI wu
+    auto thgrad = [&](const double (&wx)[4], double wu) __attribute__((always_inline)) {
+        double v = 0.0;
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) v += cst[NO_L + c2] * wx[c2];
+        return -v - psi * wu;
+    };
+    for (int k = 0; k < N; ++k) {
+        const double vk = zsh[k];
+        double wx[4];
+        xgrad(NO_Q, x, wx);
+        const double lr = cst[NO_R];
+        const double eu = lr * (vk - psi * th);
+        J += eu * eu;
+        const double wu = 2.0 * lr * eu;
+        const double wt = thgrad(wx, wu);
+        double xn[4], AB[4][5];
+        nm_rk4<true>(a.delta, x, vk + ueq, xn, AB);
+        // the lane's entry of the record, picked by compares (no indexed register array)
+        double rv = 0.0;
+#pragma unroll
+        for (int l = 0; l < 16; ++l) rv = lane == l ? AB[l & 3][l >> 2] : rv;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rv = lane == 16 + i ? AB[i][4] : rv;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rv = lane == 20 + i ? wx[i] : rv;
+        rv = lane == 24 ? wu : rv;
+        rv = lane == 25 ? wt : rv;
+        if (rec) rec[(int64_t)k * rstride] = rv;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = xn[i];
+        // row `lane` of stage k + 1: F_x (x_{k+1} - x_eq) <= h_x, F_u (u_k - u_eq) <= h_u
+        if (lane < ms) {
+            double cv;
+            if (lane < mx) {
+                cv = -cst[NO_HX + lane];
+#pragma unroll
+                for (int c2 = 0; c2 < 4; ++c2) cv += cst[NO_FX + lane + mx * c2] * (x[c2] - cst[NO_XE + c2]);
+            } else {
+                cv = cst[NO_FU + lane - mx] * vk - cst[NO_HU + lane - mx];
+            }
+            rhs[nmpc_stage_row(mx, mu, k + 1, lane)] = -cv;
+            bnd[(int64_t)k * bstride] = nmpc_bound_value(map, lane, -cv);
+        }
+    }
+    // terminal P on x_N, T on LAMBDA theta: w_N = [2 Lp'e; 0; -LAMBDA'(2 Lp'e) + 2 (Lt LAMBDA)'(Lt LAMBDA) theta]
+    {
+        double wx[4];
+        xgrad(NO_P, x, wx);
+        double wt = thgrad(wx, 0.0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double w = 0.0;
+#pragma unroll
+            for (int c2 = r; c2 < 4; ++c2) w += cst[NO_T + 4 * r + c2] * cst[NO_L + c2];
+            const double e = w * th;
+            J += e * e;
+            wt += 2.0 * w * e;
+        }
+        double rv = 0.0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rv = lane == 20 + i ? wx[i] : rv;
+        rv = lane == 25 ? wt : rv;
+        if (lane >= 20 && lane < 26) rec[(int64_t)N * rstride] = rv;
+    }
+    // terminal rows F_T [x_N - x_eq; theta] <= h_T, lanes over the rows
+    const int64_t rT = nmpc_term_row(N, mx, mu, 0);
+    double* hp = s.hp + (int64_t)b * mp;
+    for (int r = lane; r < mp; r += NM_WAVE) {
+        double F[5];
+#pragma unroll
+        for (int c2 = 0; c2 < 5; ++c2) F[c2] = a.FT[r + (int64_t)mp * c2];
+        double cv = F[4] * th - a.hT[r];
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) cv += F[c2] * (x[c2] - cst[NO_XE + c2]);
+        rhs[rT + r] = -cv;
+        hp[r] = -cv;
+    }
+    if (lane == 0) a.cost0[b] = J;
+}
+
+// After the structured solve, one wave per instance (a finished instance leaves at once): the step
+// d = [du; dtheta], the multipliers in NMPC row order through the bound map, the sub-problem's
+// exit flag, and by one backward adjoint sweep over A_k, B_k the condensed gradient f (from the
+// w_k) and C'lam (from the multipliers) that nmpc_update_kernel<true> reads:
+//   p_N = x part (+ F_x'lam_N + F_T[:, :4]'lam_T),  g_k = u part + B_k'p_{k+1} (+ F_u lam),
+//   p_k = x part + A_k'p_{k+1} (+ F_x'lam_k),  theta entry = sum of the theta parts (+ F_T[:, 4]'lam_T)
+__global__ void __launch_bounds__(64) nmpc_stage_backmap_kernel(NmpcArgs a, NmpcStageArgs s) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    if (b >= a.batch || a.done[b]) return;
+    const int N = a.N, n = a.n, m = a.m, mx = a.mx, mu = a.mu, mp = a.mp;
+    __shared__ NmpcBoundMap map;
+    __shared__ double gf[NM_WAVE * NM_CPL], gl[NM_WAVE * NM_CPL];
+    nm_load_map(s.map, lane, &map);
+    wave_sync();
+    const double* uo = s.uo + (int64_t)b * N;
+    const double* lamx = s.lamx + (int64_t)b * (N + 1) * 8;
+    const double* lamu = s.lamu + (int64_t)b * N * 2;
+    const double* lamp = s.lamp + (int64_t)b * mp;
+    double* d = a.d + (int64_t)b * n;
+    double* lam = a.lam + (int64_t)b * m;
+    for (int j = lane; j < N; j += NM_WAVE) d[j] = uo[j];
+    if (lane == 0) {
+        d[N] = s.tho[b];
+        a.qpflag[b] = s.sflag[b];
+    }
+    for (int r = lane; r < m; r += NM_WAVE) lam[r] = nmpc_stage_dual(map, N, mx, mu, r, lamx, lamu, lamp);
+    // F_T'lam_T: lanes over the rows, five wave sums
+    double tT[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int r = lane; r < mp; r += NM_WAVE) {
+        const double lr = lamp[r];
+#pragma unroll
+        for (int c2 = 0; c2 < 5; ++c2) tT[c2] = fma(a.FT[r + (int64_t)mp * c2], lr, tT[c2]);
+    }
+#pragma unroll
+    for (int c2 = 0; c2 < 5; ++c2) tT[c2] = wsum(tT[c2]);
+    // per (variable, side) the row's entry of F_x / F_u and its scale (0 and 1 where no row is):
+    // the row's share of C'lam is entry * (bound multiplier / scale), as lam above
+    double Fe[NMS_NVAR][2], sc[NMS_NVAR][2];
+#pragma unroll
+    for (int v = 0; v < NMS_NVAR; ++v)
+#pragma unroll
+        for (int sd = 0; sd < 2; ++sd) {
+            const int i = map.rowof[v][sd];
+            Fe[v][sd] = i < 0 ? 0.0 : (v < 4 ? a.Fx[i + mx * v] : a.Fu[i - mx]);
+            sc[v][sd] = i < 0 ? 1.0 : map.scale[i];
+        }
+    auto xrows = [&](int k, double (&p)[4]) __attribute__((always_inline)) {   // p += F_x'lam_k
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            p[v] += Fe[v][0] * (lamx[nmpc_lamx_index(k, 0, v)] / sc[v][0]) +
+                    Fe[v][1] * (lamx[nmpc_lamx_index(k, 1, v)] / sc[v][1]);
+    };
+    const double* A = s.A + (int64_t)b * N * 16;
+    const double* B = s.B + (int64_t)b * N * 4;
+    const double* w = s.w + (int64_t)b * (N + 1) * 6;
+    double pf[4], pl[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { pf[i] = w[6 * N + i]; pl[i] = tT[i]; }
+    xrows(N, pl);
+    double thf = w[6 * N + 5];
+    for (int k = N - 1; k >= 0; --k) {
+        double Ak[16], Bk[4], wk[6];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) Ak[i] = A[16 * k + i];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) Bk[i] = B[4 * k + i];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) wk[i] = w[6 * k + i];
+        double g1 = wk[4], g2 = Fe[4][0] * (lamu[nmpc_lamu_index(k, 0)] / sc[4][0]) +
+                                Fe[4][1] * (lamu[nmpc_lamu_index(k, 1)] / sc[4][1]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { g1 += Bk[i] * pf[i]; g2 += Bk[i] * pl[i]; }
+        if (lane == 0) { gf[k] = g1; gl[k] = g2; }
+        thf += wk[5];
+        if (k > 0) {
+            double qf[4], ql[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                double v1 = wk[j], v2 = 0.0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { v1 += Ak[i + 4 * j] * pf[i]; v2 += Ak[i + 4 * j] * pl[i]; }
+                qf[j] = v1; ql[j] = v2;
+            }
+            xrows(k, ql);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { pf[j] = qf[j]; pl[j] = ql[j]; }
+        }
+    }
+    if (lane == 0) { gf[N] = thf; gl[N] = tT[4]; }
+    wave_sync();
+    for (int j = lane; j < n; j += NM_WAVE) {
+        a.f[(int64_t)b * n + j] = gf[j];
+        a.ctl[(int64_t)b * n + j] = gl[j];
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // launch helpers
 // ------------------------------------------------------------------------------------------
+static bool nmpc_stage_args_ok(const NmpcArgs& a) {
+    return nmpc_supported(a.N, a.mx, a.mu) && a.n == a.N + 1 && a.m == a.N * (a.mx + a.mu) + a.mp &&
+           a.n <= NM_WAVE * NM_CPL && a.mx + a.mu <= NM_WAVE && a.batch >= 1 && a.mp >= 0;
+}
+
+hipError_t launch_nmpc_stage_table(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st) {
+    if (!nmpc_stage_args_ok(a) || !s.W || !s.map || (a.mp > 0 && !s.Fp)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_stage_table_kernel, dim3(1), dim3(64), 0, st, a, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_stage_rollout(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st) {
+    if (!nmpc_stage_args_ok(a) || !s.A || !s.B || !s.w || !s.xlb || !s.xub || !s.ulb || !s.uub ||
+        (a.mp > 0 && !s.hp) || !s.map || !a.rhs || !a.cost0)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_stage_rollout_kernel, dim3(a.batch), dim3(64), 0, st, a, s);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_stage_backmap(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st) {
+    if (!nmpc_stage_args_ok(a) || !s.uo || !s.tho || !s.lamx || !s.lamu || (a.mp > 0 && !s.lamp) ||
+        !s.sflag || !s.map || !a.ctl || !a.f || !a.d || !a.lam)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_stage_backmap_kernel, dim3(a.batch), dim3(64), 0, st, a, s);
+    return hipGetLastError();
+}
+
 bool nmpc_supported(int N, int mx, int mu) {
     return N >= 1 && N <= NMPC_MAXN && N + 1 <= NM_WAVE * NM_CPL && mx >= 0 && mx <= NMPC_MAXMX &&
            mu >= 0 && mu <= NMPC_MAXMU;
@@ -514,7 +875,9 @@ hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st) {
 
 hipError_t launch_nmpc_update(const NmpcArgs& a, hipStream_t st) {
     if (a.n > NM_WAVE * NM_CPL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nmpc_update_kernel, dim3(a.batch), dim3(64), 0, st, a);
+    if (a.C) hipLaunchKernelGGL(nmpc_update_kernel<false>, dim3(a.batch), dim3(64), 0, st, a);
+    else if (a.ctl) hipLaunchKernelGGL(nmpc_update_kernel<true>, dim3(a.batch), dim3(64), 0, st, a);
+    else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 

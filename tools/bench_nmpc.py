@@ -8,9 +8,15 @@ Warmed up; timed with the library's device events around work that ends in a syn
   --batch B --steps S --warmup W   sizes (defaults 256, 100, 1)
   --sync     the closed loop step-synchronous (BQP_NMPC_SYNC set for the loop run alone; the
              default is the asynchronous loop); `loop_rounds` is printed in both modes
+  --subproblem dense|stage   how the SQP's sub-problems are solved (default dense): condensed on
+             the dense kernels, or in stage form on the structured kernel with per-stage models
+  --polish P the sub-problems' polish (bqp_options.polish; default 0)
   --split    also the split of an SQP iteration over linearise / normal equations / dense /
-             trials / update: a child process runs the cold solves with BQP_LB_TRACE=2 and its
-             per-iteration lines are summed here
+             trials / update (stage route: stage linearisation / structured solve / back-map /
+             trials / update): a child process runs the cold solves with BQP_LB_TRACE=2 and its
+             per-iteration lines are summed here, per iteration index too (the first is the cold
+             one); the stage route's child also reports the workspace bytes it reserved
+  --dump F   X, U, exitflag, iterations of the loop into the .npz file F
 The bytes of the dense solve's stream of the instances' C are computed from the shapes."""
 import argparse
 import json
@@ -48,9 +54,9 @@ def starts(batch, seed=11):
     return np.ascontiguousarray(x)
 
 
-def child(batch):
+def child(batch, subproblem, polish):
     import bqp
-    bqp.NMPC.solve(problem(), starts(batch), handle=bqp.Handle(0))
+    bqp.NMPC.solve(problem(), starts(batch), handle=bqp.Handle(0), subproblem=subproblem, polish=polish)
 
 
 def main():
@@ -61,9 +67,12 @@ def main():
     ap.add_argument('--sync', action='store_true')
     ap.add_argument('--split', action='store_true')
     ap.add_argument('--child', action='store_true')
+    ap.add_argument('--subproblem', choices=('dense', 'stage'), default='dense')
+    ap.add_argument('--polish', type=int, default=0)
+    ap.add_argument('--dump', default=None)
     a = ap.parse_args()
     if a.child:
-        return child(a.batch)
+        return child(a.batch, a.subproblem, a.polish)
     import torch
     assert torch.cuda.is_available(), 'bench_nmpc.py needs a GPU'
     import bqp
@@ -71,25 +80,27 @@ def main():
     g = problem()
     x = starts(a.batch)
     for _ in range(a.warmup):
-        g.solve(x, handle=h)
+        g.solve(x, handle=h, subproblem=a.subproblem, polish=a.polish)
     lib = bqp.load()
     import ctypes as C
     from bqp import _lib
     # the solve alone (g.solve also rolls the solution out for y_OL): events around the SQP
     z = np.zeros((a.batch, N + 1)); lam = np.zeros((a.batch, g.m)); cost = np.zeros(a.batch)
     fl = np.zeros(a.batch, np.int32); it = np.zeros(a.batch, np.int32)
-    dims, dd, o = g._dims(), g._data(x), _lib.options(max_iter=100, tol_stat=1e-8, polish=0)
+    dims, dd = g._dims(a.subproblem), g._data(x)
+    o = _lib.options(max_iter=100, tol_stat=1e-8, polish=a.polish)
     _lib.check(lib.bqp_nmpc_solve_batched(h.value, C.byref(dims), a.batch, C.byref(dd), C.byref(o),
                                           _lib.ptr(z), _lib.ptr(lam), _lib.ptr(cost), _lib.iptr(fl),
                                           _lib.iptr(it)), 'bqp_nmpc_solve_batched')
     ms, launches = h.kernel_ms()
-    out = dict(N=N, batch=a.batch, m=g.m, solve_ms=ms, solves_per_s=a.batch / ms * 1e3,
+    out = dict(N=N, batch=a.batch, m=g.m, subproblem=a.subproblem, polish=a.polish, solve_ms=ms, solves_per_s=a.batch / ms * 1e3,
                solve_iterations_mean=float(it.mean()), solve_iterations_max=int(it.max()),
                solve_converged=float((fl == 1).mean()), solve_launches=launches,
                solve_flags={str(int(k)): int((fl == k).sum()) for k in np.unique(fl)})
     # per SQP iteration the dense solve reads the instance's C (m x n doubles) once per
     # interior-point iteration at least: bytes per pass over the batch, from the shapes
-    out['C_bytes_per_pass'] = int(a.batch) * g.m * (N + 1) * 8
+    if a.subproblem == 'dense':
+        out['C_bytes_per_pass'] = int(a.batch) * g.m * (N + 1) * 8
     if a.steps > 0:
         rng = np.random.default_rng(12)
         xnl = np.load(os.path.join(ROOT, 'tests', 'golden', 'nmpc_DSS_tNMPC.npz'))['xnl']
@@ -100,8 +111,8 @@ def main():
             os.environ['BQP_NMPC_SYNC'] = '1'
         try:
             if a.warmup:
-                bqp.closed_loop_nmpc(g, xi, 2, handle=h)
-            r = bqp.closed_loop_nmpc(g, xi, a.steps, handle=h)
+                bqp.closed_loop_nmpc(g, xi, 2, handle=h, subproblem=a.subproblem, polish=a.polish)
+            r = bqp.closed_loop_nmpc(g, xi, a.steps, handle=h, subproblem=a.subproblem, polish=a.polish)
         finally:
             os.environ.pop('BQP_NMPC_SYNC', None)
         out.update(loop_mode='sync' if a.sync else 'async', loop_steps=a.steps, loop_ms=r.kernel_ms,
@@ -112,22 +123,38 @@ def main():
                    instance_steps_per_s=a.batch * a.steps / r.kernel_ms * 1e3,
                    loop_iterations_mean=float(r.iterations.mean()),
                    loop_iterations_max=int(r.iterations.max()),
+                   loop_at_iteration_limit=int((r.exitflag == 0).sum()),
                    loop_converged=float((r.exitflag == 1).mean()), loop_launches=r.launches)
+        if a.dump:
+            np.savez(a.dump, X=r.X, U=r.U, exitflag=r.exitflag, iterations=r.iterations)
     if a.split:
         env = dict(os.environ, BQP_LB_TRACE='2')
-        c = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--batch', str(a.batch)],
+        c = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--batch', str(a.batch),
+                            '--subproblem', a.subproblem, '--polish', str(a.polish)],
                            env=env, capture_output=True, text=True, timeout=600, check=True)
-        names = ('linearise', 'normal', 'dense', 'trials', 'update')
+        if a.subproblem == 'dense':
+            names = ('linearise', 'normal', 'dense', 'trials', 'update')
+            pat = (r'bqp nmpc it (\d+) ms: linearise ([\d.]+) normal ([\d.]+) dense\(\+polish\) ([\d.]+) '
+                   r'trials ([\d.]+) update ([\d.]+)')
+        else:
+            names = ('stage_linearise', 'structured', 'back_map', 'trials', 'update')
+            pat = (r'bqp nmpc it (\d+) ms: stage-linearise ([\d.]+) structured\(\+repair\) ([\d.]+) '
+                   r'back-map ([\d.]+) trials ([\d.]+) update ([\d.]+)')
         tot = dict.fromkeys(names, 0.0)
-        rows = 0
+        per_it = []
         for line in c.stderr.splitlines():
-            mt = re.match(r'bqp nmpc it \d+ ms: linearise ([\d.]+) normal ([\d.]+) dense\(\+polish\) ([\d.]+) '
-                          r'trials ([\d.]+) update ([\d.]+)', line)
+            mt = re.match(pat, line)
             if mt:
-                rows += 1
-                for k, v in zip(names, mt.groups()):
-                    tot[k] += float(v)
+                vals = [float(v) for v in mt.groups()[1:]]
+                per_it.append(dict(zip(names, vals)))
+                for k, v in zip(names, vals):
+                    tot[k] += v
+            mw = re.match(r'bqp nmpc stage route: workspace (\d+) bytes', line)
+            if mw:
+                out['stage_workspace_bytes'] = int(mw.group(1))
+        rows = len(per_it)
         out['split_ms_per_iteration'] = {k: v / max(rows, 1) for k, v in tot.items()}
+        out['split_ms_by_iteration'] = per_it
         out['split_iterations'] = rows
     print(json.dumps(out))
 
