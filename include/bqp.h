@@ -147,6 +147,25 @@ typedef struct {
                            not solved and none of its outputs is written (finished instances
                            of an outer iteration).  Non-NULL with stage_models = 0 is
                            BQP_E_UNSUPPORTED */
+    /* Soft state bounds (both NULL, a zero-initialised caller: every bound is hard).  With weights
+     * l1 = xs_lin, l2 = xs_quad >= 0 per state variable and stage the problem becomes
+     *   min cost + sum_{k=1..N, i, side} (l1_{k,i} s + 0.5 l2_{k,i} s^2)
+     *   s.t. xlb_{k,i} - s^l_{k,i} <= x_{k,i} <= xub_{k,i} + s^u_{k,i},  s >= 0
+     * (an exact L1 plus quadratic penalty; each finite side has its own slack; a variable whose
+     * weights are both 0 keeps hard bounds; input bounds and polytope rows are always hard).
+     * Each array is (N+1)*nx (stage 0 unused), stride sxs (0 = shared by the batch, otherwise
+     * >= (N+1)*nx); either pointer NULL = zeros.  A negative or non-finite weight is BQP_E_ARG on
+     * the host entry points; on the device entry points it is the caller's duty.
+     * fval includes the penalty; bqp_output.constrviolation measures the softened rows
+     * (x - s <= xub), not the slack; the softened rows' stationarity l1 + l2 s - lam - nu joins the
+     * stop test and bqp_output.firstorderopt.  Limits: fp64 only (bqp_options.precision 1 or 2
+     * returns BQP_E_UNSUPPORTED); bqp_options.polish is taken as -1 and bqp_output.polished is 0 (an
+     * active-set polish of softened rows does not exist yet); one model or
+     * stage_models = 1, N <= 127, both families; honoured by bqp_closed_loop_ocp and
+     * bqp_closed_loop_track, while bqp_closed_loop_lbmpc returns BQP_E_UNSUPPORTED; no MEX field. */
+    const double* xs_lin;
+    const double* xs_quad;
+    int64_t sxs;
 } bqp_ocp_data;
 
 /* Optional multiplier outputs of the structured solve (NULL members are skipped).  Sign
@@ -157,6 +176,10 @@ typedef struct {
     double* lam_x;  /* batch*(N+1)*nx*2: [lower, upper] per stage (0 for absent bounds) */
     double* lam_u;  /* batch*N*nu*2                                                    */
     double* lam_p;  /* batch*n_poly                                                    */
+    double* s_x;    /* batch*(N+1)*nx*2, layout of lam_x: the slacks of the softened state rows
+                       (bqp_ocp_data.xs_lin / xs_quad), 0 for hard or absent rows; written by a
+                       soft solve only.  lam_x of a softened row is the multiplier of the softened
+                       row; at the optimum it lies in [0, l1 + l2 s] */
 } bqp_ocp_duals;
 
 /* Lifecycle.  device < 0 selects the current HIP device. */

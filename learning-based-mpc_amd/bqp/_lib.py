@@ -39,11 +39,11 @@ class OcpDims(C.Structure):
 class OcpData(C.Structure):
     _fields_ = [(n, _PD) for n in ('A', 'B', 'c', 'W', 'w', 'xlb', 'xub', 'ulb', 'uub', 'Fp', 'hp', 'x0')] + \
                [(n, C.c_int64) for n in ('sA', 'sB', 'sc', 'sW', 'sw', 'sxb', 'sub', 'sFp', 'shp', 'sx0')] + \
-               [('skip', _PI)]
+               [('skip', _PI), ('xs_lin', _PD), ('xs_quad', _PD), ('sxs', C.c_int64)]
 
 
 class OcpDuals(C.Structure):
-    _fields_ = [('pi', _PD), ('lam_x', _PD), ('lam_u', _PD), ('lam_p', _PD)]
+    _fields_ = [('pi', _PD), ('lam_x', _PD), ('lam_u', _PD), ('lam_p', _PD), ('s_x', _PD)]
 
 
 class Dims(C.Structure):

@@ -21,10 +21,14 @@ class OcpProblem:
     box bounds on x_k (k>=1), u_k; polytope Fp [x_kp; u_kp; theta] <= hp.
 
     Arrays use natural numpy shapes (row-major): W (N+1, nv, nv), w (N+1, nv),
-    xlb/xub (N+1, nx), ulb/uub (N, nu), Fp (mp, nv), hp (mp,)."""
+    xlb/xub (N+1, nx), ulb/uub (N, nu), Fp (mp, nv), hp (mp,).
+
+    xs_lin, xs_quad (N+1, nx), weights >= 0: soft state bounds (bqp_ocp_data.xs_lin / xs_quad) -
+    xlb - s_l <= x <= xub + s_u with the penalty l1 s + 0.5 l2 s^2 on every slack; a variable whose
+    weights are both 0 keeps hard bounds.  Structured kernel only, fp64, no polish."""
 
     def __init__(self, A, B, W, N, np_, w=None, c=None, xlb=None, xub=None, ulb=None, uub=None,
-                 Fp=None, hp=None, poly_stage=None, const=0.0):
+                 Fp=None, hp=None, poly_stage=None, const=0.0, xs_lin=None, xs_quad=None):
         self.A = np.asarray(A, float)
         self.B = np.asarray(B, float)
         self.nx, self.nu = self.B.shape
@@ -44,6 +48,12 @@ class OcpProblem:
         self.hp = np.zeros(0) if hp is None else np.asarray(hp, float).ravel()
         self.poly_stage = self.N if poly_stage is None else int(poly_stage)
         self.const = const
+        self.xs_lin = None if xs_lin is None else np.asarray(xs_lin, float).reshape(self.N + 1, self.nx)
+        self.xs_quad = None if xs_quad is None else np.asarray(xs_quad, float).reshape(self.N + 1, self.nx)
+
+    @property
+    def soft(self):
+        return self.xs_lin is not None or self.xs_quad is not None
 
     @property
     def mp(self):
@@ -85,14 +95,15 @@ def _stage_models(prob, batch, A, B, c, stage_models):
 
 
 def pack(prob, x0, w=None, hp=None, A=None, B=None, Fp=None, W=None, c=None, stage_models=None,
-         skip=None):
+         skip=None, xs_lin=None, xs_quad=None):
     """Builds (dims, data, keepalive) for a batch.  x0: (batch, nx); per-instance overrides
     w (batch, N+1, nv), hp (batch, mp), A (batch, nx, nx), B (batch, nx, nu), c (batch, nx) and the
     polytope Fp (batch, mp, nv) (same row count and stage as prob's) and the stage costs W (batch,
     N+1, nv, nv).  Per-stage models (bqp_ocp_dims.stage_models = 1): A (N, nx, nx), B (N, nx, nu),
     c (N, nx) as one schedule for the batch, or (batch, N, ...) per instance; what is not given is
     prob's model repeated over the stages.  skip (batch,) ints: with per-stage models, instances
-    that are not solved."""
+    that are not solved.  xs_lin, xs_quad (batch, N+1, nx): per-instance soft-bound weights
+    in place of prob's (what is not given is prob's, or zeros)."""
     x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
     batch = x0.shape[0]
     keep = [x0]
@@ -136,6 +147,23 @@ def pack(prob, x0, w=None, hp=None, A=None, B=None, Fp=None, W=None, c=None, sta
         if sk.shape != (batch,):
             raise ValueError('skip must have one entry per instance')
         keep.append(sk)
+    # soft state bounds: prob's weights shared by the batch, or per-instance overrides
+    xl = getattr(prob, 'xs_lin', None) if xs_lin is None else xs_lin
+    xq = getattr(prob, 'xs_quad', None) if xs_quad is None else xs_quad
+    sxs = 0
+    if xl is not None or xq is not None:
+        per = any(a is not None and np.ndim(a) == 3 for a in (xl, xq))
+
+        def wts(a):
+            if a is None:
+                return None
+            a = np.asarray(a, float)
+            if a.shape not in ((N + 1, nx), (batch, N + 1, nx)):
+                raise ValueError('soft-bound weights of shape %r, expected %r or %r'
+                                 % (a.shape, (N + 1, nx), (batch, N + 1, nx)))
+            return arr(np.broadcast_to(a, (batch, N + 1, nx)) if per else a)
+        xl, xq = wts(xl), wts(xq)
+        sxs = (N + 1) * nx if per else 0
     dims = _lib.OcpDims(nx, nu, prob.np, N, mp, prob.poly_stage, 1 if stg else 0)
     data = _lib.OcpData(
         A=_lib.ptr(Aa), B=_lib.ptr(Ba), c=_lib.ptr(ca), W=_lib.ptr(Wa), w=_lib.ptr(wa),
@@ -144,14 +172,19 @@ def pack(prob, x0, w=None, hp=None, A=None, B=None, Fp=None, W=None, c=None, sta
         sA=sA, sB=sB, sc=sc,
         sW=0 if W is None else (N + 1) * nv * nv,
         sw=0 if w is None else (N + 1) * nv, sxb=0, sub=0, sFp=0 if Fp is None else mp * nv,
-        shp=0 if hp is None else mp, sx0=nx, skip=_lib.iptr(sk) if sk is not None else None)
+        shp=0 if hp is None else mp, sx0=nx, skip=_lib.iptr(sk) if sk is not None else None,
+        xs_lin=_lib.ptr(xl), xs_quad=_lib.ptr(xq), sxs=sxs)
     return dims, data, batch, keep
 
 
 def solve_ocp(prob, x0, w=None, hp=None, A=None, B=None, handle=None, want_duals=False, Fp=None,
-              W=None, route='auto', c=None, stage_models=None, skip=None, **opts):
+              W=None, route='auto', c=None, stage_models=None, skip=None, xs_lin=None, xs_quad=None,
+              **opts):
     """Solve a batch on the GPU.  Returns OcpResult(x (b,N+1,nx), u (b,N,nu), theta (b,np),
-    fval, exitflag, iterations, firstorderopt, constrviolation, mu[, pi, lam_x, lam_u, lam_p]).
+    fval, exitflag, iterations, firstorderopt, constrviolation, mu[, pi, lam_x, lam_u, lam_p, s_x]).
+    xs_lin, xs_quad: per-instance soft-bound weights (batch, N+1, nx) in place of prob's; a soft
+    problem runs on the structured kernel only (the condensed route raises ValueError), and s_x
+    (b, N+1, 2, nx) [lower, upper] holds the slacks of the softened rows.
     A, B, c: one model (nx, nx) / (batch, nx, nx), or per-stage models (linear time-varying)
     (N, nx, nx) / (batch, N, nx, nx) - see pack; per-stage models run on the structured kernel
     only, in fp64.  skip: with per-stage models, instances left unsolved
@@ -162,7 +195,8 @@ def solve_ocp(prob, x0, w=None, hp=None, A=None, B=None, handle=None, want_duals
         raise ValueError("route must be 'auto', 'structured' or 'condensed', not %r" % (route,))
     lib = _lib.load()
     h = handle or _default_handle()
-    dims, data, batch, keep = pack(prob, x0, w, hp, A, B, Fp, W, c, stage_models, skip)
+    dims, data, batch, keep = pack(prob, x0, w, hp, A, B, Fp, W, c, stage_models, skip, xs_lin, xs_quad)
+    soft = bool(data.xs_lin) or bool(data.xs_quad)
     N, nx, nu, npar, mp = prob.N, prob.nx, prob.nu, prob.np, prob.mp
     x = np.zeros((batch, N + 1, nx)); u = np.zeros((batch, N, nu)); th = np.zeros((batch, npar))
     fval = np.zeros(batch); flag = np.zeros(batch, np.int32)
@@ -173,7 +207,12 @@ def solve_ocp(prob, x0, w=None, hp=None, A=None, B=None, handle=None, want_duals
         dd = dict(pi=np.zeros((batch, N, nx)), lam_x=np.zeros((batch, N + 1, 2, nx)),
                   lam_u=np.zeros((batch, N, 2, nu)), lam_p=np.zeros((batch, max(mp, 1))))
         duals = _lib.OcpDuals(*(_lib.ptr(dd[k]) for k in ('pi', 'lam_x', 'lam_u', 'lam_p')))
+        if soft:
+            dd['s_x'] = np.zeros((batch, N + 1, 2, nx))
+            duals.s_x = _lib.ptr(dd['s_x'])
     if route == 'condensed':
+        if soft:
+            raise ValueError('condensed route: soft state bounds run on the structured kernel only')
         if c is not None or dims.stage_models:
             raise ValueError('condensed route: only x0 and hp may vary per instance')
         return solve_ocp_condensed(prob, x0, w, hp, A, B, handle, want_duals, Fp, W, **opts)
@@ -183,7 +222,7 @@ def solve_ocp(prob, x0, w=None, hp=None, A=None, B=None, handle=None, want_duals
                                    _lib.iptr(flag), out, C.byref(duals) if duals else None)
     # the condensed route takes only x0 and hp per instance: anything else keeps the structured
     # solver's own error (an LDS fit failure is not a reason to change the algorithm)
-    condensable = all(v is None for v in (w, A, B, Fp, W, c)) and not want_duals
+    condensable = all(v is None for v in (w, A, B, Fp, W, c)) and not want_duals and not soft
     if rc == _lib.BQP_E_UNSUPPORTED and route == 'auto' and condensable and \
             not _lib.ocp_dims_supported(prob.nx, prob.nu, prob.np, prob.N, prob.mp):
         return solve_ocp_condensed(prob, x0, w, hp, A, B, handle, want_duals, Fp, W, **opts)
@@ -234,6 +273,8 @@ def solve_ocp_condensed(prob, x0, w=None, hp=None, A=None, B=None, handle=None, 
     from .quadprog import quadprog
     if any(a is not None for a in (w, A, B, Fp, W)):
         raise ValueError('condensed route: only x0 and hp may vary per instance')
+    if getattr(prob, 'soft', False):
+        raise ValueError('condensed route: soft state bounds run on the structured kernel only')
     if want_duals:
         raise ValueError('condensed route: stage-wise multipliers are not returned '
                          '(bqp.quadprog gives the condensed rows\' multipliers)')

@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "../../include/bqp.h"
@@ -287,6 +288,9 @@ int bqp_last_loop_rounds(bqp_handle h, int* rounds) {
 // ------------------------------------------------------------------------------------------
 // structured OCP
 // ------------------------------------------------------------------------------------------
+// soft state bounds: a weight array is given (bqp_ocp_data.xs_lin / xs_quad)
+static bool ocp_soft(const bqp_ocp_data* D) { return D->xs_lin || D->xs_quad; }
+
 static int ocp_check(const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D) {
     if (!d || !D || batch <= 0) return BQP_E_ARG;
     if (d->nx <= 0 || d->nu <= 0 || d->np <= 0 || d->N < 1 || d->n_poly < 0) return BQP_E_ARG;
@@ -308,6 +312,19 @@ static int ocp_check(const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D) {
     } else if (D->skip) {
         return BQP_E_UNSUPPORTED;
     }
+    // soft state bounds: a per-instance stride spans the instance's (N + 1) nx weights
+    if (ocp_soft(D) && (D->sxs < 0 || (D->sxs != 0 && D->sxs < (int64_t)(d->N + 1) * d->nx))) return BQP_E_ARG;
+    return BQP_OK;
+}
+
+// host entry points: every weight finite and >= 0 (the device entries leave that to the caller)
+static int ocp_soft_host_check(const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D) {
+    if (!ocp_soft(D)) return BQP_OK;
+    const size_t n = (size_t)(d->N + 1) * d->nx, tot = D->sxs == 0 ? n : (size_t)(batch - 1) * (size_t)D->sxs + n;
+    for (const double* w : {D->xs_lin, D->xs_quad})
+        if (w)
+            for (size_t i = 0; i < tot; ++i)
+                if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return BQP_E_ARG;
     return BQP_OK;
 }
 
@@ -328,8 +345,12 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
     if (o.precision < 0 || o.precision > 2) return BQP_E_ARG;
     // per-stage models: fp64 instantiations only (their repair launch carries the per-stage
     // models: the polish runs on the same Riccati routines as the solve)
-    const bool stg = d->stage_models == 1;
+    // soft state bounds: the soft instantiations are per-stage-model ones (a one-model problem reads
+    // block 0 of A, B, c at every stage), fp64, without the active-set polish
+    const bool soft = ocp_soft(D);
+    const bool stg = d->stage_models == 1 || soft;
     if (stg && o.precision != 0) return BQP_E_UNSUPPORTED;
+    if (soft) o.polish = -1;
     const bool f32 = o.precision == 1;     // fp32 instantiation (bqp_ocp_f32.hip)
     // fp32 phase, then fp64 from the fp32 iterate; long horizons only (N + 1 > 64, the
     // instantiations that carry the handoff): shorter ones are solved in fp64 alone
@@ -460,6 +481,12 @@ int bqp_solve_ocp_batched_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
     if (fpi) { a.Fp_inst = D->Fp; a.sFp = D->sFp; }
     a.stage_models = stg ? 1 : 0;
     a.skip = stg ? D->skip : nullptr;
+    if (soft) {
+        a.soft = 1;
+        a.one_model = d->stage_models == 1 ? 0 : 1;
+        a.xs_lin = D->xs_lin; a.xs_quad = D->xs_quad; a.sxs = D->sxs;
+        a.sx_out = duals ? duals->s_x : nullptr;
+    }
     a.x = x; a.u = u; a.theta = theta; a.fval = fval; a.exitflag = exitflag; a.stats = Sd;
     if (duals) {
         a.pi_out = duals->pi; a.lamx_out = duals->lam_x; a.lamu_out = duals->lam_u;
@@ -543,6 +570,8 @@ static void stage_ocp_data(Stage& st, const bqp_ocp_dims* d, int batch, const bq
     st.in(&Dd->hp, D->hp, span(batch, D->shp, mp));
     st.in(&Dd->x0, x0, nx0);
     st.in(&Dd->skip, D->skip, (size_t)batch);
+    st.in(&Dd->xs_lin, D->xs_lin, span(batch, D->sxs, (N + 1) * nx));
+    st.in(&Dd->xs_quad, D->xs_quad, span(batch, D->sxs, (N + 1) * nx));
 }
 
 int bqp_solve_ocp_batched(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D,
@@ -551,6 +580,7 @@ int bqp_solve_ocp_batched(bqp_handle h, const bqp_ocp_dims* d, int batch, const 
                           const bqp_ocp_duals* duals) {
     if (!h) return BQP_E_ARG;
     BQP_TRY(ocp_check(d, batch, D));
+    BQP_TRY(ocp_soft_host_check(d, batch, D));
     if (!x || !u || !theta || !exitflag) return BQP_E_ARG;
     DevScope ds(h->device);
     const size_t B = batch, nx = d->nx, nu = d->nu, np = d->np, N = d->N, mp = d->n_poly;
@@ -577,6 +607,7 @@ int bqp_solve_ocp_batched(bqp_handle h, const bqp_ocp_dims* d, int batch, const 
         res(&dd.lam_x, B * (N + 1) * nx * 2, duals->lam_x, alignof(double));
         res(&dd.lam_u, B * N * nu * 2, duals->lam_u, alignof(double));
         res(&dd.lam_p, B * mp, duals->lam_p, alignof(double));
+        if (duals->s_x) res(&dd.s_x, B * (N + 1) * nx * 2, duals->s_x, alignof(double));
     }
     res(&ed, B, exitflag, alignof(int));
     res(&od, B, out, 64);
@@ -977,6 +1008,7 @@ static int closed_loop_impl(bqp_handle h, const bqp_ocp_dims* d, int batch, cons
     if (!h || !cl || !x_init || !X || !U) return BQP_E_ARG;
     BQP_TRY(ocp_check(d, batch, D));
     if (d->stage_models) return BQP_E_UNSUPPORTED;   // per-stage models: the plain solves only
+    if (lw && ocp_soft(D)) return BQP_E_UNSUPPORTED;  // soft state bounds: not in the learned-model loop
     BQP_TRY(loop_check(cl, d->nx, d->nu));
     if (lw && (lw->q < 1 || lw->q > (1 << 20) || !lw->XL)) return BQP_E_ARG;
     DevScope ds(h->device);
@@ -1044,6 +1076,8 @@ static int closed_loop_host(bqp_handle h, const bqp_ocp_dims* d, int batch, cons
     if (lw && (lw->q < 1 || lw->q > (1 << 20) || !lw->XL)) return BQP_E_ARG;
     BQP_TRY(ocp_check(d, batch, D));
     if (d->stage_models) return BQP_E_UNSUPPORTED;   // per-stage models: the plain solves only
+    if (lw && ocp_soft(D)) return BQP_E_UNSUPPORTED;  // soft state bounds: not in the learned-model loop
+    BQP_TRY(ocp_soft_host_check(d, batch, D));
     // validate the loop description before sizing the staging buffers from it
     BQP_TRY(loop_check(cl, d->nx, d->nu));
     DevScope ds(h->device);
@@ -1185,6 +1219,7 @@ int bqp_closed_loop_track(bqp_handle h, const bqp_ocp_dims* d, int batch, const 
                           const double* x_init, double* X, double* U, int* exitflag) {
     // validate the whole description before sizing the staging buffers from it
     BQP_TRY(track_check(h, d, batch, D, cl, tr, x_init, X, U));
+    BQP_TRY(ocp_soft_host_check(d, batch, D));
     DevScope ds(h->device);
     const size_t B = batch, S = cl->steps, nx = d->nx, nu = d->nu, np = d->np;
     const size_t nw = (size_t)(d->N + 1) * (nx + nu + np), nr = tr->nr;
@@ -1578,6 +1613,7 @@ static int nmpc_stage_setup(bqp_handle h, const bqp_nmpc_dims* d, int batch, con
     R.fv = layout::at<double>(nw, NL.fv);
     R.sflag = layout::at<int>(nw, NL.sflag);
     R.du.pi = nullptr;
+    R.du.s_x = nullptr;
     R.du.lam_x = layout::at<double>(nw, NL.lamx);
     R.du.lam_u = layout::at<double>(nw, NL.lamu);
     R.du.lam_p = layout::at<double>(nw, NL.lamp);

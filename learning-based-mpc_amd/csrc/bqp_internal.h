@@ -81,6 +81,15 @@ struct OcpKernelArgs {
     // skip[i] != 0 (may be null) leave at once without writing an output
     int stage_models;
     const int* skip;
+    // soft state bounds (bqp_ocp_data.xs_lin / xs_quad; fp64, plain grid, no polish): soft = 1 runs
+    // the soft instantiations, which are per-stage-model ones; one_model = 1 hands them a one-model
+    // problem (every stage reads block 0 of A, B, c).  xs_lin / xs_quad: (N+1) nx weights per
+    // instance (stride sxs; either may be null = zeros); sx_out (may be null): the slacks in the
+    // layout of lamx_out
+    int soft, one_model;
+    const double *xs_lin, *xs_quad;
+    int64_t sxs;
+    double* sx_out;
 };
 
 bool ocp_supported(int nx, int nu, int np);

@@ -243,6 +243,11 @@ enum : int {
 // two polish-only slots
 constexpr int X_NEXT = X_PVA;
 static_assert(X_PVIOL == X_PVA + 1, "X_NEXT + 1 must be a polish-only slot");
+// soft state bounds (the SOFT instantiations are solve kernels, never repair or queue kernels, so
+// two polish-only slots carry their exchange): max |l1 + l2 s - lam - nu| over the softened rows
+// and the penalty sum (l1 s + l2 s^2 / 2) of the iterate (row wave, per iteration)
+constexpr int X_RSS = X_PLNEG;
+constexpr int X_PEN = X_PLMX;
 
 // Per-instance LDS layout (in doubles), sized from N at run time.
 struct QpLds {
@@ -391,7 +396,11 @@ __device__ __forceinline__ bool hand_warm(const OcpKernelArgs& a, int inst) {
 // polish runs on factor / prep_iter / solve / stage_partials, which read the stage's model):
 // every read of Abar / Bbar / cbar is a read of stage k's model, from the instance's LDS table
 // (N + 1 <= 64) or from the caller's arrays in global memory (long horizons).
-template <int NX, int NU, int NP, int SPL, bool POL, int G, bool STG = false>
+// SOFT: soft state bounds (bqp_ocp_data.xs_lin / xs_quad; STG solve kernels only).  The stage wave
+// reads the same Dx / blam / ebox tables; the softened rows' stationarity residual joins its stop
+// test, their penalty its fval, and a one-model problem (OcpKernelArgs::one_model) reads block 0 of
+// A, B, c at every stage.
+template <int NX, int NU, int NP, int SPL, bool POL, int G, bool STG = false, bool SOFT = false>
 __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, const QpLds& L,
                                            const real* Hs, int lane_w, int inst, int pslot) {
     const int lane = lane_w;
@@ -405,6 +414,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     // the sweeps carry the stage's model in their DPP form only; the plain form (fp32) reads the
     // one model of the solve and must never be compiled into a per-stage instantiation
     static_assert(!STG || SWEEP_DPP_FMAC, "per-stage models: the sweeps' DPP form only");
+    static_assert(!SOFT || (STG && !POL), "soft state bounds: per-stage-model solve kernels only");
     constexpr int ES = lanes::entries_per_lane(NS, G);   // s-part entries per lane
     const int N = a.N, kp = a.kp, hstride = a.hstride;
     // the stage a lane serves (> N: none); j: second stage of the lane at SPL = 2
@@ -446,10 +456,12 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         if constexpr (!LNG) {
             for (int t = lane; t < N * MW; t += WAVE) {
                 const int k = t / MW, e = t - k * MW;
+                int kg = k;                               // the block of the caller's arrays
+                if constexpr (SOFT) { if (a.one_model) kg = 0; }
                 real v;
-                if (e < NX * NX) v = Ag[(int64_t)k * (NX * NX) + e];
-                else if (e < NX * NX + NX * NU) v = Bg[(int64_t)k * (NX * NU) + (e - NX * NX)];
-                else v = cg ? cg[(int64_t)k * NX + (e - NX * NX - NX * NU)] : 0.0;
+                if (e < NX * NX) v = Ag[(int64_t)kg * (NX * NX) + e];
+                else if (e < NX * NX + NX * NU) v = Bg[(int64_t)kg * (NX * NU) + (e - NX * NX)];
+                else v = cg ? cg[(int64_t)kg * NX + (e - NX * NX - NX * NU)] : 0.0;
                 W[L.AB + k * MST + e] = v;
             }
         }
@@ -473,9 +485,11 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     auto mdl = [&](int k, int e) __attribute__((always_inline)) -> real {
         const int km = k < N ? k : N - 1;
         if constexpr (LNG) {
-            if (e < NX * NX) return (real)Ag[(int64_t)km * (NX * NX) + e];
-            if (e < NX * NX + NX * NU) return (real)Bg[(int64_t)km * (NX * NU) + (e - NX * NX)];
-            return cg ? (real)cg[(int64_t)km * NX + (e - NX * NX - NX * NU)] : real(0);
+            int kg = km;
+            if constexpr (SOFT) { if (a.one_model) kg = 0; }
+            if (e < NX * NX) return (real)Ag[(int64_t)kg * (NX * NX) + e];
+            if (e < NX * NX + NX * NU) return (real)Bg[(int64_t)kg * (NX * NU) + (e - NX * NX)];
+            return cg ? (real)cg[(int64_t)kg * NX + (e - NX * NX - NX * NU)] : real(0);
         } else {
             return W[L.AB + km * MST + e];
         }
@@ -1725,6 +1739,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         BARRIER();                                        // B0: row multipliers / D / F'DF, row residual norm, comp sum ready
         STAMP(0);
         stat = combine();
+        if constexpr (SOFT) stat = fmax(stat, X[X_RSS]);  // the softened rows' own stationarity
         STAMP(1);
         STAMP(2);
         feq = feasA;
@@ -1984,6 +1999,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
         }
     }
     fv = wsum(fv);
+    if constexpr (SOFT) fv += X[X_PEN];                   // the iterate's penalty (row wave, before B0)
     STAMP_STORE(0);
     if (lane == 0) {
         if (a.fval) a.fval[inst] = fv;
@@ -2003,9 +2019,18 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
 // ==========================================================================================
 // row wave
 // ==========================================================================================
-template <int NX, int NU, int NP, int BPL, int RPL, bool POL>
+// SOFT: soft state bounds.  A softened box row  +-v - s + t = +-bd  carries (t, lam, s, nu) with the
+// residuals r_p = +-v - s + t -+ bd, r_s = l1 + l2 s - lam - nu and the pairs t lam, s nu.  Its
+// Newton equations  +-dv - ds + dt = -r_p,  l2 ds - dlam - dnu = -r_s,  t dlam + lam dt = -rc_t,
+// s dnu + nu ds = -rc_s  are reduced in the row: with E = l2 + nu / s, g = r_s + rc_s / s,
+//   t~ = t + lam / E,  r~ = r_p + g / E,
+//   dlam = D (+-dv) + e,  D = lam / t~,  e = (lam r~ - rc_t) / t~       (the hard row's form),
+//   ds = (dlam - g) / E,  dnu = (-rc_s - nu ds) / s,  dt = -r_p -+ dv + ds,
+// so the stage wave's tables Dx / blam / ebox keep their meaning.  A row with l1 = l2 = 0 is hard.
+template <int NX, int NU, int NP, int BPL, int RPL, bool POL, bool SOFT = false>
 __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const QpLds& L,
                                          const real* Fs, const real* Sh, int lane, int inst) {
+    static_assert(!SOFT || (!POL && sizeof(real) == 8), "soft state bounds: fp64 solve kernels only");
     constexpr bool PC = POL && BQP_POLISH && !BQP_EXP_NOROW;
     constexpr int NS = NX + NP;
     constexpr int NV = NS + NU;
@@ -2091,6 +2116,30 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
         }
     }
     mcount += __builtin_popcount(bmsk);
+    // SOFT: the weights of the lane's box variables (both rows of a variable share them), the
+    // softened rows smsk (present state rows with a positive weight) and their slack s and its
+    // multiplier nu.  son: the rows that currently run the soft form - none while the starting
+    // point is formed (the rows are taken as hard there), smsk from then on.  Every softened row
+    // adds its second pair s nu to the row count behind mu
+    unsigned smsk = 0, son = 0;
+    real sx[BPL], sn[BPL], w1[BPL / 2], w2[BPL / 2];
+    if constexpr (SOFT) {
+#pragma unroll
+        for (int pv = 0; pv < BPL / 2; ++pv) {
+            const int vi = lane + WAVE * pv, k = vi / NB, sl = vi - k * NB;
+            w1[pv] = 0.0; w2[pv] = 0.0;
+            if (sl < NX && k >= 1 && k <= N) {
+                const int64_t o = (int64_t)inst * a.sxs + (int64_t)k * NX + sl;
+                if (a.xs_lin) w1[pv] = a.xs_lin[o];
+                if (a.xs_quad) w2[pv] = a.xs_quad[o];
+            }
+            if (w1[pv] > 0.0 || w2[pv] > 0.0) smsk |= bmsk & (3u << (2 * pv));
+        }
+#pragma unroll
+        for (int b = 0; b < BPL; ++b) { sx[b] = 1.0; sn[b] = 1.0; }
+        mcount += __builtin_popcount(smsk);
+    }
+    auto bsoft = [&](int b) __attribute__((always_inline)) -> bool { return (son >> b) & 1u; };
     // theta entries of the per-stage diagonal D never change
     for (int k = lane; k <= N; k += WAVE) {
 #pragma unroll
@@ -2157,8 +2206,25 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
 
     // ---- multiplier-side tables (depend on t, lam only): box multipliers, Fp'lam, 1/t,
     //      D = lam/t per stage, F'DF, sum t.lam ----
+    // SOFT, a softened row's share of the tables: D = lam / t~, both pairs in the complementarity
+    // sum and maximum, |r_s| and the penalty of the iterate
+    auto soft_tab = [&](int b, real& d, real& cs, real& cm, real& rsm, real& pen) __attribute__((always_inline)) {
+        const int pv = b >> 1;
+        const real iE = frcp(w2[pv] + sn[b] * frcp(sx[b]));
+        d += lx[b] * frcp(tx[b] + lx[b] * iE);
+        cs += tx[b] * lx[b] + sx[b] * sn[b];
+        cm = fmax(cm, fmax(tx[b] * lx[b], sx[b] * sn[b]));
+        rsm = fmax(rsm, fabs(w1[pv] + w2[pv] * sx[b] - lx[b] - sn[b]));
+        pen += (w1[pv] + 0.5 * w2[pv] * sx[b]) * sx[b];
+    };
+    auto soft_publish = [&](real rsm, real pen) __attribute__((always_inline)) {
+        rsm = wmax(rsm);
+        pen = wsum(pen);
+        if (lane == 0) { X[X_RSS] = rsm; X[X_PEN] = pen; }
+    };
     auto lam_side = [&]() __attribute__((always_inline)) {
         real cs = 0.0, cm = 0.0;
+        [[maybe_unused]] real rsm = 0.0, pen = 0.0;
 #pragma unroll
         for (int pv = 0; pv < BPL / 2; ++pv) {
             ROW_FENCE(pv);
@@ -2167,11 +2233,14 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int b = 2 * pv + h;
-                if (bpres(b)) {
+                bool sf = false;
+                if constexpr (SOFT) sf = bsoft(b);
+                if (bpres(b) && !sf) {
                     d += lx[b] * frcp(tx[b]);
                     cs += tx[b] * lx[b];
                     if constexpr (BQP_POLISH) cm = fmax(cm, tx[b] * lx[b]);
                 }
+                if constexpr (SOFT) { if (sf) soft_tab(b, d, cs, cm, rsm, pen); }
                 if constexpr (LNG) {
                     if (bpres(b)) blv += h ? -lx[b] : lx[b];
                 } else {
@@ -2183,6 +2252,7 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
             }
             if (binrange(2 * pv)) W[dx_off(pv)] = d;
         }
+        if constexpr (SOFT) soft_publish(rsm, pen);
         real gpp[NV];
         real fd[NV * (NV + 1) / 2];
 #pragma unroll
@@ -2245,7 +2315,9 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
     auto box_res = [&](int b) __attribute__((always_inline)) -> real {
         const real v = bvar(b, L.xs, L.xu);
         const real bd = bndp[brow(b)];
-        return (bcode(b) & 1) == 0 ? v + tx[b] - bd : -v + tx[b] + bd;
+        real r = (bcode(b) & 1) == 0 ? v + tx[b] - bd : -v + tx[b] + bd;
+        if constexpr (SOFT) { if (bsoft(b)) r -= sx[b]; }   // softened row: +-v - s + t -+ bd
+        return r;
     };
     // ---- row residuals of the current iterate (box: +-v + t -+ b; polytope: Fp v + t - hp) ----
     auto row_residuals = [&]() __attribute__((always_inline)) {
@@ -2288,6 +2360,67 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
         return socf * box_pred_raw(b);
     };
 
+    // ---- SOFT: a softened row's reduction (see the head of row_wave) ----
+    struct SoftRow { real rp, g, iE, tt, is; };          // r_p, g = r_s + rc_s / s, 1 / E, t~, 1 / s
+    struct SoftDir { real dt, dl, ds, dn; };
+    auto soft_row = [&](int b, real rcs) __attribute__((always_inline)) -> SoftRow {
+        const int pv = b >> 1;
+        SoftRow o;
+        o.is = frcp(sx[b]);
+        o.iE = frcp(w2[pv] + sn[b] * o.is);
+        o.tt = tx[b] + lx[b] * o.iE;
+        o.rp = box_res(b);
+        o.g = (w1[pv] + w2[pv] * sx[b] - lx[b] - sn[b]) + rcs * o.is;
+        return o;
+    };
+    // e of the row for the complementarity right-hand sides (rc_t; rc_s is in r.g)
+    auto soft_eterm = [&](int b, const SoftRow& r, real rct) __attribute__((always_inline)) -> real {
+        return (lx[b] * (r.rp + r.g * r.iE) - rct) * frcp(r.tt);
+    };
+    // the row's steps along the direction (ids, idu)
+    auto soft_dir = [&](int b, const SoftRow& r, real rct, real rcs, int ids, int idu) __attribute__((always_inline)) -> SoftDir {
+        const real dv = bvar(b, ids, idu);
+        const real sdv = (bcode(b) & 1) == 0 ? dv : -dv;
+        SoftDir d;
+        d.dl = (lx[b] * (sdv + r.rp + r.g * r.iE) - rct) * frcp(r.tt);
+        d.ds = (d.dl - r.g) * r.iE;
+        d.dn = (-rcs - sn[b] * d.ds) * r.is;
+        d.dt = -r.rp - sdv + d.ds;
+        return d;
+    };
+    // predictor products dt_a dlam_a and ds_a dnu_a (recomputed from the predictor direction)
+    auto soft_pred = [&](int b, real& prt, real& prs) __attribute__((always_inline)) {
+        const real rct = tx[b] * lx[b], rcs = sx[b] * sn[b];
+        const SoftRow r = soft_row(b, rcs);
+        const SoftDir d = soft_dir(b, r, rct, rcs, L.dsv, L.duv);
+        prt = d.dt * d.dl;
+        prs = d.ds * d.dn;
+    };
+    // complementarity right-hand sides of the two pairs (rcv for each)
+    auto soft_rc = [&](int b, bool corr, real smu, real& rct, real& rcs) __attribute__((always_inline)) {
+        rct = tx[b] * lx[b];
+        rcs = sx[b] * sn[b];
+        if (corr) {
+            real prt, prs;
+            soft_pred(b, prt, prs);
+            rct += socf * prt - smu;
+            rcs += socf * prs - smu;
+        }
+    };
+    // max of the four step ratios
+    auto soft_ratio = [&](int b, const SoftDir& d, real acc) __attribute__((always_inline)) -> real {
+        acc = fmax(acc, -d.dt * frcp(tx[b]));
+        acc = fmax(acc, -d.dl * frcp(lx[b]));
+        acc = fmax(acc, -d.ds * frcp(sx[b]));
+        return fmax(acc, -d.dn * frcp(sn[b]));
+    };
+    auto soft_step = [&](int b, const SoftDir& d, real al) __attribute__((always_inline)) {
+        tx[b] += al * d.dt;
+        lx[b] += al * d.dl;
+        sx[b] += al * d.ds;
+        sn[b] += al * d.dn;
+    };
+
     // ---- right-hand-side terms (lam o ri - rc)/t: box [upper, lower] per stage, Fp'e ----
     auto rhs_terms = [&](bool corr, real smu) __attribute__((always_inline)) {
         real eacc = 0.0;
@@ -2296,9 +2429,18 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
             ROW_FENCE(b);
             if (!binrange(b)) continue;
             real e = 0.0;
-            if (bpres(b)) {
+            bool sf = false;
+            if constexpr (SOFT) sf = bsoft(b);
+            if (bpres(b) && !sf) {
                 const real pr = corr ? box_pred_prod(b) : 0.0;
                 e = (lx[b] * box_res(b) - rcv(tx[b], lx[b], pr, corr, smu)) * frcp(tx[b]);
+            }
+            if constexpr (SOFT) {
+                if (sf) {
+                    real rct, rcs;
+                    soft_rc(b, corr, smu, rct, rcs);
+                    e = soft_eterm(b, soft_row(b, rcs), rct);
+                }
             }
             if constexpr (LNG) {
                 if ((b & 1) == 0) eacc = e;
@@ -2334,6 +2476,21 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
         for (int b = 0; b < BPL; ++b) {
             ROW_FENCE(b);
             if (!bpres(b)) continue;
+            if constexpr (SOFT) {
+                if (bsoft(b)) {
+                    real rct, rcs;
+                    soft_rc(b, corr, smu, rct, rcs);
+                    const SoftRow r = soft_row(b, rcs);
+                    const SoftDir d = soft_dir(b, r, rct, rcs, ids, idu);
+                    if (mode == 0) {
+                        acc = soft_ratio(b, d, acc);
+                    } else {
+                        acc = fmax(acc, fabs((1.0 - al) * r.rp));
+                        soft_step(b, d, al);
+                    }
+                    continue;
+                }
+            }
             const real pr = corr ? box_pred_prod(b) : 0.0;
             const real rc = rcv(tx[b], lx[b], pr, corr, smu);
             const real dt = box_dir(b, ids, idu);
@@ -2388,7 +2545,23 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
             ROW_FENCE(b);
             if (!binrange(b)) continue;
             real e0 = 0.0;
-            if (bpres(b)) {
+            bool sf = false;
+            if constexpr (SOFT) sf = bsoft(b);
+            if constexpr (SOFT) {
+                if (sf) {
+                    // both pairs in the ratio test and in S2; the corrector term with both
+                    // second-order products, sigma mu still to come (rhs_corr_finish)
+                    const real rct = tx[b] * lx[b], rcs = sx[b] * sn[b];
+                    SoftRow r = soft_row(b, rcs);
+                    const SoftDir d = soft_dir(b, r, rct, rcs, L.dsv, L.duv);
+                    rm = soft_ratio(b, d, rm);
+                    const real prt = d.dt * d.dl, prs = d.ds * d.dn;
+                    s2 += prt + prs;
+                    r.g += prs * r.is;
+                    e0 = soft_eterm(b, r, rct + prt);
+                }
+            }
+            if (bpres(b) && !sf) {
                 const real t = tx[b], l = lx[b];
                 const real it = frcp(t);
                 const real rc = t * l;
@@ -2448,6 +2621,17 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
         for (int b = 0; b < BPL; ++b) {
             ROW_FENCE(b);
             if (!bpres(b)) continue;
+            if constexpr (SOFT) {
+                if (bsoft(b)) {
+                    real rct, rcs;
+                    soft_rc(b, true, smu, rct, rcs);
+                    const SoftRow r = soft_row(b, rcs);
+                    const SoftDir d = soft_dir(b, r, rct, rcs, L.dsc, L.duc);
+                    fe = fmax(fe, fabs((1.0 - al) * r.rp));
+                    soft_step(b, d, al);
+                    continue;
+                }
+            }
             const real pr = box_pred_prod(b);
             const real rc = rcv(tx[b], lx[b], pr, true, smu);
             const real dt = box_dir(b, L.dsc, L.duc);
@@ -2465,6 +2649,7 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
     //      then Fp'lam, F'DF, sum t.lam exactly as lam_side; feb = the box rows' residual norm ----
     auto poly_apply_lam = [&](real smu, real al, real feb) __attribute__((always_inline)) {
         real cs = 0.0, cm = 0.0;
+        [[maybe_unused]] real rsm = 0.0, pen = 0.0;
 #pragma unroll
         for (int pv = 0; pv < BPL / 2; ++pv) {
             ROW_FENCE(pv);
@@ -2472,11 +2657,14 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int b = 2 * pv + h;
-                if (bpres(b)) {
+                bool sf = false;
+                if constexpr (SOFT) sf = bsoft(b);
+                if (bpres(b) && !sf) {
                     d += lx[b] * frcp(tx[b]);
                     cs += tx[b] * lx[b];
                     if constexpr (BQP_POLISH) cm = fmax(cm, tx[b] * lx[b]);
                 }
+                if constexpr (SOFT) { if (sf) soft_tab(b, d, cs, cm, rsm, pen); }
                 if constexpr (LNG) {
                     if (bpres(b)) blv += h ? -lx[b] : lx[b];
                 } else {
@@ -2488,6 +2676,7 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
             }
             if (binrange(2 * pv)) W[dx_off(pv)] = d;
         }
+        if constexpr (SOFT) soft_publish(rsm, pen);
         real gpp[NV];
         real fdt[NV * (NV + 1) / 2];
 #pragma unroll
@@ -2553,19 +2742,44 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
         }
     };
 
+    // d e / d (sigma mu) of a box row: 1 / t; softened row: (1 - lam / (s E)) / t~ (both pairs'
+    // right-hand sides carry -sigma mu)
+    auto smu_coef = [&](int b) __attribute__((always_inline)) -> real {
+        if constexpr (SOFT) {
+            if (bsoft(b)) {
+                const real is = frcp(sx[b]);
+                const real iE = frcp(w2[b >> 1] + sn[b] * is);
+                return (1.0 - lx[b] * iE * is) * frcp(tx[b] + lx[b] * iE);
+            }
+        }
+        return frcp(tx[b]);
+    };
+    // the second-order products' share of e, to be taken back out by rhs_drop_soc
+    auto soc_term = [&](int b) __attribute__((always_inline)) -> real {
+        if constexpr (SOFT) {
+            if (bsoft(b)) {
+                real prt, prs;
+                soft_pred(b, prt, prs);
+                const real is = frcp(sx[b]);
+                const real iE = frcp(w2[b >> 1] + sn[b] * is);
+                return (prt - lx[b] * prs * iE * is) * frcp(tx[b] + lx[b] * iE);
+            }
+        }
+        return box_pred_raw(b) * frcp(tx[b]);
+    };
     auto rhs_corr_finish = [&](real smu, real tot) __attribute__((always_inline)) {
         if constexpr (LNG) {
 #pragma unroll
             for (int pv = 0; pv < BPL / 2; ++pv) {
                 real add = 0.0;
-                if (bpres(2 * pv)) add += smu * frcp(tx[2 * pv]);
-                if (bpres(2 * pv + 1)) add -= smu * frcp(tx[2 * pv + 1]);
+                if (bpres(2 * pv)) add += smu * smu_coef(2 * pv);
+                if (bpres(2 * pv + 1)) add -= smu * smu_coef(2 * pv + 1);
                 if (binrange(2 * pv)) W[L.ebox + lane + WAVE * pv] += add;
             }
         } else {
 #pragma unroll
             for (int b = 0; b < BPL; ++b)
-                if (bpres(b)) W[L.ebox + brow(b)] += smu * frcp(tx[b]);
+                if (bpres(b)) W[L.ebox + brow(b)] += smu * smu_coef(b);
         }
         // tot (from the joint reduction): lane 2c = Fp'e0 (c), lane 2c+1 = Fp'(1/t) (c)
         const real other = dpp_mov0<0xB1>(tot);
@@ -2578,14 +2792,14 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
 #pragma unroll
             for (int pv = 0; pv < BPL / 2; ++pv) {
                 real add = 0.0;
-                if (bpres(2 * pv)) add += box_pred_raw(2 * pv) * frcp(tx[2 * pv]);
-                if (bpres(2 * pv + 1)) add -= box_pred_raw(2 * pv + 1) * frcp(tx[2 * pv + 1]);
+                if (bpres(2 * pv)) add += soc_term(2 * pv);
+                if (bpres(2 * pv + 1)) add -= soc_term(2 * pv + 1);
                 if (binrange(2 * pv)) W[L.ebox + lane + WAVE * pv] += add;
             }
         } else {
 #pragma unroll
             for (int b = 0; b < BPL; ++b)
-                if (bpres(b)) W[L.ebox + brow(b)] += box_pred_raw(b) * frcp(tx[b]);
+                if (bpres(b)) W[L.ebox + brow(b)] += soc_term(b);
         }
         real gc[NV];
 #pragma unroll
@@ -2654,6 +2868,7 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
 #pragma unroll
             for (int q = 0; q < RPL; ++q)
                 if (prow(q)) { RP(q) += shp; fe = fmax(fe, fabs(RP(q))); }
+            if constexpr (SOFT) { if (smsk) fe = fmax(fe, fabs(shp - 1.0)); }   // r_p with s = 1 (below)
             fe = wmax(fe);
             if (lane == 0) X[X_FEASB] = fe;
         }
@@ -2671,6 +2886,16 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
             const bool pr = prow(q);
             tp[q] = pr ? t + shp : 1.0;
             lp[q] = pr ? -t + shd : 0.0;
+        }
+        if constexpr (SOFT) {
+            // the softened rows took the start as hard rows (son = 0); from here they run the soft
+            // form, from s = 1 and nu = l1 + l2 s - lam (r_s = 0) where that is at least 1
+            son = smsk;
+#pragma unroll
+            for (int b = 0; b < BPL; ++b) {
+                sx[b] = 1.0;
+                sn[b] = bsoft(b) ? fmax(w1[b >> 1] + w2[b >> 1] - lx[b], 1.0) : 1.0;
+            }
         }
     }
     lam_side();
@@ -2762,6 +2987,10 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
             const real lv = bpres(b) ? lb[b] : 0.0;      // layout per stage: [lower; upper]
             if (sl < NX) {
                 if (a.lamx_out) a.lamx_out[((int64_t)inst * (N + 1) + k) * NX * 2 + (h ? sl : NX + sl)] = lv;
+                if constexpr (SOFT) {
+                    if (a.sx_out)
+                        a.sx_out[((int64_t)inst * (N + 1) + k) * NX * 2 + (h ? sl : NX + sl)] = bsoft(b) ? sx[b] : 0.0;
+                }
             } else if (k < N) {
                 if (a.lamu_out) a.lamu_out[((int64_t)inst * N + k) * NU * 2 + (h ? sl - NX : NU + sl - NX)] = lv;
             }
@@ -3139,7 +3368,7 @@ __device__ __forceinline__ void row_wave(const OcpKernelArgs& a, real* W, const 
 // ==========================================================================================
 // kernel: QPB instances per workgroup, waves [0, QPB) stage waves, [QPB, 2 QPB) row waves
 // ==========================================================================================
-template <int NX, int NU, int NP, int SPL, int RPL, int BPL, bool POL, bool QUEUE, int G, bool STG = false>
+template <int NX, int NU, int NP, int SPL, int RPL, int BPL, bool POL, bool QUEUE, int G, bool STG = false, bool SOFT = false>
 __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
     constexpr int NS = NX + NP;
     constexpr int NV = NS + NU;
@@ -3255,13 +3484,13 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
         if (rowwave && lane == 0)
             *reinterpret_cast<int*>(W + L.xch + X_NEXT + xnext) = atomicAdd(a.queue, 1) + (int)gridDim.x * qpb;
 #if defined(BQP_EXP_ONLY)   // register-budget diagnostic: one wave's code alone (never run)
-        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL, G, STG>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
-        else row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fsi, lds, lane, inst);
+        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL, G, STG, SOFT>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
+        else row_wave<NX, NU, NP, BPL, RPL, POL, SOFT>(a, W, L, Fsi, lds, lane, inst);
 #else
         if (!rowwave)
-            stage_wave<NX, NU, NP, SPL, POL, G, STG>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
+            stage_wave<NX, NU, NP, SPL, POL, G, STG, SOFT>(a, W, L, Hs, lane, inst, blockIdx.x * qpb + slot0);
         else
-            row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fsi, lds, lane, inst);
+            row_wave<NX, NU, NP, BPL, RPL, POL, SOFT>(a, W, L, Fsi, lds, lane, inst);
 #endif
         return W + L.xch;
     };
@@ -3298,13 +3527,13 @@ __device__ __forceinline__ void ocp_body(const OcpKernelArgs& a) {
             wave_sync();
         }
 #if defined(BQP_EXP_ONLY)   // register-budget diagnostic: one wave's code alone (never run)
-        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL, G, STG>(a, W, L, Hs, lane, inst, inst);
-        else row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fs, lds, lane, inst);
+        if (BQP_EXP_ONLY == 1) stage_wave<NX, NU, NP, SPL, POL, G, STG, SOFT>(a, W, L, Hs, lane, inst, inst);
+        else row_wave<NX, NU, NP, BPL, RPL, POL, SOFT>(a, W, L, Fs, lds, lane, inst);
 #else
         if (!rowwave)
-            stage_wave<NX, NU, NP, SPL, POL, G, STG>(a, W, L, Hs, lane, inst, inst);
+            stage_wave<NX, NU, NP, SPL, POL, G, STG, SOFT>(a, W, L, Hs, lane, inst, inst);
         else
-            row_wave<NX, NU, NP, BPL, RPL, POL>(a, W, L, Fs, lds, lane, inst);
+            row_wave<NX, NU, NP, BPL, RPL, POL, SOFT>(a, W, L, Fs, lds, lane, inst);
 #endif
     } else {
         // persistent work queue (ocp_queue_kernel; launch_t sizes the grid to the resident
@@ -3349,6 +3578,12 @@ template <int NX, int NU, int NP, int SPL, int RPL, int BPL, int G, bool STG = f
 __global__ void __launch_bounds__(SPL == 2 ? 256 : 512) ocp_ipm_kernel(OcpKernelArgs a) {
     ocp_body<NX, NU, NP, SPL, RPL, BPL, false, false, G, STG>(a);
 }
+// the soft-state-bound solve kernel: per-stage models (a one-model problem reads block 0), one
+// instance per slot, no repair launch (the polish is off on soft problems)
+template <int NX, int NU, int NP, int SPL, int RPL, int BPL>
+__global__ void __launch_bounds__(SPL == 2 ? 256 : 512) ocp_soft_kernel(OcpKernelArgs a) {
+    ocp_body<NX, NU, NP, SPL, RPL, BPL, false, false, 1, true, true>(a);
+}
 template <int NX, int NU, int NP, int SPL, int RPL, int BPL, int G, bool STG = false>
 __global__ void __launch_bounds__(SPL == 2 ? 256 : 512) ocp_polish_kernel(OcpKernelArgs a) {
     ocp_body<NX, NU, NP, SPL, RPL, BPL, true, false, G, STG>(a);
@@ -3373,12 +3608,15 @@ ocp_queue_kernel(OcpKernelArgs a) {
 // The kernel instantiations are split over translation units by model family so that the
 // build compiles them in parallel (Makefile: BQP_FAMILY=1 MG nx4/nu1/np1 with the dispatcher
 // and host helpers, BQP_FAMILY=2 DI nx2/nu2/np2); without BQP_FAMILY one unit holds all.
-// The per-stage-model instantiations (fp64 only) are units of their own: BQP_FAMILY=3 MG, 4 DI.
+// The per-stage-model instantiations (fp64 only) are units of their own: BQP_FAMILY=3 MG, 4 DI,
+// and so are the soft-state-bound ones (fp64 only): BQP_FAMILY=5 MG, 6 DI.
 #if !defined(BQP_FAMILY)
 #define BQP_FAM_MG 1
 #define BQP_FAM_DI 1
 #define BQP_FAM_STG_MG 1
 #define BQP_FAM_STG_DI 1
+#define BQP_FAM_SOFT_MG 1
+#define BQP_FAM_SOFT_DI 1
 #elif BQP_FAMILY == 1
 #define BQP_FAM_MG 1
 #define BQP_FAM_DI 0
@@ -3389,10 +3627,18 @@ ocp_queue_kernel(OcpKernelArgs a) {
 #define BQP_FAM_MG 0
 #define BQP_FAM_DI 0
 #define BQP_FAM_STG_MG 1
-#else
+#elif BQP_FAMILY == 4
 #define BQP_FAM_MG 0
 #define BQP_FAM_DI 0
 #define BQP_FAM_STG_DI 1
+#elif BQP_FAMILY == 5
+#define BQP_FAM_MG 0
+#define BQP_FAM_DI 0
+#define BQP_FAM_SOFT_MG 1
+#else
+#define BQP_FAM_MG 0
+#define BQP_FAM_DI 0
+#define BQP_FAM_SOFT_DI 1
 #endif
 #ifndef BQP_FAM_STG_MG
 #define BQP_FAM_STG_MG 0
@@ -3400,11 +3646,21 @@ ocp_queue_kernel(OcpKernelArgs a) {
 #ifndef BQP_FAM_STG_DI
 #define BQP_FAM_STG_DI 0
 #endif
+#ifndef BQP_FAM_SOFT_MG
+#define BQP_FAM_SOFT_MG 0
+#endif
+#ifndef BQP_FAM_SOFT_DI
+#define BQP_FAM_SOFT_DI 0
+#endif
 #if defined(BQP_F32) || defined(BQP_ISA_ONLY_MG10) || defined(BQP_ISA_ONLY_MG_LNG) || defined(BQP_ISA_ONLY_DI)
 #undef BQP_FAM_STG_MG
 #undef BQP_FAM_STG_DI
+#undef BQP_FAM_SOFT_MG
+#undef BQP_FAM_SOFT_DI
 #define BQP_FAM_STG_MG 0
 #define BQP_FAM_STG_DI 0
+#define BQP_FAM_SOFT_MG 0
+#define BQP_FAM_SOFT_DI 0
 #endif
 
 // dynamic LDS of a launch: the kernel's static LDS must fit beside it (a launch past 160 KB is
@@ -3548,6 +3804,50 @@ hipError_t launch_ocp_stg_di(const OcpKernelArgs& a, int spl, int rpl, int block
 }
 #endif
 
+// soft state bounds (OcpKernelArgs::soft): the soft solve kernel, one instance per slot
+template <int NX, int NU, int NP, int SPL, int BPL>
+[[maybe_unused]] static hipError_t launch_soft_rpl(const OcpKernelArgs& a0, int rpl, int blocks, size_t lds, hipStream_t st) {
+#ifndef BQP_F32
+    OcpKernelArgs a = a0;
+    a.queue = nullptr;
+    auto go = [&](auto k) -> hipError_t {
+        if (hipError_t e = lds_attr((const void*)k, lds)) return e;
+        hipLaunchKernelGGL(k, dim3(blocks), dim3(128 * a.wpb), lds, st, a);
+        return hipGetLastError();
+    };
+    switch (rpl) {
+        case 1: return go(dp::ocp_soft_kernel<NX, NU, NP, SPL, 1, BPL>);
+        case 4: return go(dp::ocp_soft_kernel<NX, NU, NP, SPL, 4, BPL>);
+        case 10: return go(dp::ocp_soft_kernel<NX, NU, NP, SPL, 10, BPL>);
+        case 16: return go(dp::ocp_soft_kernel<NX, NU, NP, SPL, 16, BPL>);
+        default: return hipErrorInvalidValue;
+    }
+#else
+    return hipErrorInvalidValue;
+#endif
+}
+template <int NX, int NU, int NP>
+[[maybe_unused]] static hipError_t launch_soft_spl(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st) {
+    const int nbr = (a.N + 1) * 2 * (NX + NU);
+    if (spl == 1 && nbr <= 4 * WAVE) return launch_soft_rpl<NX, NU, NP, 1, 4>(a, rpl, blocks, lds, st);
+    if (spl == 1 && nbr <= 10 * WAVE) return launch_soft_rpl<NX, NU, NP, 1, 10>(a, rpl, blocks, lds, st);
+    if (spl == 2 && nbr <= 16 * WAVE) return launch_soft_rpl<NX, NU, NP, 2, 16>(a, rpl, blocks, lds, st);
+    if (spl == 2 && nbr <= 20 * WAVE) return launch_soft_rpl<NX, NU, NP, 2, 20>(a, rpl, blocks, lds, st);
+    return hipErrorInvalidValue;
+}
+hipError_t launch_ocp_soft_mg(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st);
+hipError_t launch_ocp_soft_di(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st);
+#if BQP_FAM_SOFT_MG
+hipError_t launch_ocp_soft_mg(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st) {
+    return launch_soft_spl<4, 1, 1>(a, spl, rpl, blocks, lds, st);
+}
+#endif
+#if BQP_FAM_SOFT_DI
+hipError_t launch_ocp_soft_di(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st) {
+    return launch_soft_spl<2, 2, 2>(a, spl, rpl, blocks, lds, st);
+}
+#endif
+
 hipError_t BQP_CAT(launch_ocp_mg, BQP_SFX)(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st, bool pol);
 hipError_t BQP_CAT(launch_ocp_di, BQP_SFX)(const OcpKernelArgs& a, int spl, int rpl, int blocks, size_t lds, hipStream_t st, bool pol);
 
@@ -3633,13 +3933,19 @@ hipError_t BQP_CAT(launch_ocp, BQP_SFX)(const OcpKernelArgs& a, int nx, int nu, 
                                                                                       a.H_inst != nullptr,
                                                                                       a.stage_models != 0));
 #if !defined(BQP_F32) && !defined(BQP_ISA_ONLY_MG10) && !defined(BQP_ISA_ONLY_MG_LNG) && !defined(BQP_ISA_ONLY_DI)
+    if (a.soft) {
+        if (!a.stage_models || pol) return hipErrorInvalidValue;
+        if (nx == 4 && nu == 1 && np == 1) return launch_ocp_soft_mg(a, spl, rpl, blocks, lds, st);
+        if (nx == 2 && nu == 2 && np == 2) return launch_ocp_soft_di(a, spl, rpl, blocks, lds, st);
+        return hipErrorInvalidValue;
+    }
     if (a.stage_models) {
         if (nx == 4 && nu == 1 && np == 1) return launch_ocp_stg_mg(a, spl, rpl, blocks, lds, st, pol);
         if (nx == 2 && nu == 2 && np == 2) return launch_ocp_stg_di(a, spl, rpl, blocks, lds, st, pol);
         return hipErrorInvalidValue;
     }
 #else
-    if (a.stage_models) return hipErrorInvalidValue;
+    if (a.stage_models || a.soft) return hipErrorInvalidValue;
 #endif
     if (nx == 4 && nu == 1 && np == 1) return BQP_CAT(launch_ocp_mg, BQP_SFX)(a, spl, rpl, blocks, lds, st, pol);
 #if !defined(BQP_ISA_ONLY_MG10) && !defined(BQP_ISA_ONLY_MG_LNG)
