@@ -514,6 +514,36 @@ typedef struct {
     const double *F_T, *h_T;           /* n_poly*5 column-major ([x_N - x_eq; theta]), n_poly */
     double delta;                      /* RK4 step and running-cost weight (in Lq, Lr) */
     const double* x0; int64_t sx0;     /* measured states, absolute, 4 per instance */
+    /* Soft state rows (both NULL, a zero-initialised caller: every row is hard, and every kernel
+     * runs as it did before these members existed).  Each array holds mx doubles, one per row of
+     * F_x, shared by the batch; either pointer NULL = zeros.  With weights l1_i = xs_lin[i],
+     * l2_i = xs_quad[i] >= 0 and phi_i(s) = l1_i s + 0.5 l2_i s^2 the problem becomes
+     *   min J(z) + sum_{k=1..N} sum_{i soft} phi_i(max(c_{k,i}(z), 0))   s.t.  c_hard(z) <= 0
+     * (an exact L1 plus quadratic penalty).  A row with both weights 0 stays hard; the rows of F_u
+     * and F_T are always hard, so a start from which the terminal set cannot be reached still ends
+     * -2.  Stage route only: with subproblem = 0 the solve and loop entries return
+     * BQP_E_UNSUPPORTED.  The sub-problem's softened bounds are the structured solve's soft state
+     * bounds (bqp_ocp_data.xs_lin / xs_quad), which carry one weight pair per (stage, variable)
+     * for both sides, in the variable's units: the row a (x_v - x_eq,v) <= h gives the pair
+     * (l1 |a|, l2 a^2).  Hence the equal-pair rule: the two rows of one state variable must be
+     * softened together and give the same pair, exactly (rows +-x_v with equal weights do; rows
+     * scaled by a take l1 / |a| and l2 / a^2); one row softened and the other hard, or unequal
+     * pairs, is BQP_E_UNSUPPORTED (found on the device with the box-row flag, before the first
+     * round); a variable with a single row may be softened.
+     * cost is J + penalty.  lam keeps its layout; on a softened row it is the multiplier of the
+     * softened row, at the optimum in the subdifferential of phi_i: l1 + l2 c where c > 0, within
+     * [0, l1] at c = 0, 0 where c < 0.  exitflag -2 is a sub-problem that is infeasible in its
+     * hard rows; feasibility in the stopping test is that of the hard rows.
+     * Limits: fp64; no active-set polish of the sub-problems (the structured solve takes polish
+     * as -1 on a soft problem, so lam on softened rows is the interior point's, and the soft
+     * sub-problems are solved to a stationarity of 1e-4 opt->tol_stat, at most the structured
+     * solve's default, since nothing after them sharpens z); bqp_nmpc_linearize
+     * and bqp_nmpc_stage_qp do not read the weights.  A negative or non-finite weight is
+     * BQP_E_ARG on the host entry points; on the _device entry points it is the caller's duty.
+     * Honoured by bqp_nmpc_solve_batched[_device], bqp_closed_loop_nmpc[_device] in both loop
+     * modes, and bqp_nmpc_stage_cost; no MEX field. */
+    const double* xs_lin;
+    const double* xs_quad;
 } bqp_nmpc_data;
 
 /* Rollout and linearisation at given z (batch*n).  Outputs, each may be NULL: X (batch*(N+1)*4,
@@ -539,6 +569,13 @@ int bqp_nmpc_stage_qp_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
                              const bqp_nmpc_data* data, const double* z, double* A, double* B,
                              double* w, double* xlb, double* xub, double* ulb, double* uub,
                              double* hp, double* W, double* Fp, void* stream);
+
+/* The stage route's cost at given z (batch*n), as its stage linearisation forms it - diagnostic;
+ * d->subproblem is not read, the box-row restriction and the soft rows' pairing rule apply.
+ * cost (batch): J + penalty, what the merit function of the SQP starts from; penalty (batch): the
+ * penalty of the softened rows at z, 0 without weights.  Host entry only. */
+int bqp_nmpc_stage_cost(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
+                        const double* z, double* cost, double* penalty);
 
 /* SQP solve.  z (batch*n): in = start, out = solution; lam (batch*m, may be NULL): multipliers
  * of the rows above; cost (batch, may be NULL); exitflag: 1 converged, 0 iteration limit

@@ -84,7 +84,8 @@ class NmpcDims(C.Structure):
 class NmpcData(C.Structure):
     _fields_ = [(n, _PD) for n in ('Lq', 'Lr', 'Lp', 'Lt', 'LAMBDA', 'PSI', 'x_eq', 'u_eq', 'F_x',
                                    'h_x', 'F_u', 'h_u', 'F_T', 'h_T')] + \
-               [('delta', C.c_double), ('x0', _PD), ('sx0', C.c_int64)]
+               [('delta', C.c_double), ('x0', _PD), ('sx0', C.c_int64),
+                ('xs_lin', _PD), ('xs_quad', _PD)]     # soft state rows: mx weights each, or NULL
 
 
 EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'bqp_build_source_sha1',
@@ -97,7 +98,8 @@ EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'b
            'bqp_debug_ocp_wpb',
            'bqp_nmpc_linearize', 'bqp_nmpc_linearize_device', 'bqp_nmpc_solve_batched',
            'bqp_nmpc_solve_batched_device', 'bqp_closed_loop_nmpc', 'bqp_closed_loop_nmpc_device',
-           'bqp_last_loop_rounds', 'bqp_nmpc_stage_qp', 'bqp_nmpc_stage_qp_device']
+           'bqp_last_loop_rounds', 'bqp_nmpc_stage_qp', 'bqp_nmpc_stage_qp_device',
+           'bqp_nmpc_stage_cost']
 
 _lib = None
 
@@ -175,6 +177,8 @@ def load():
     lib.bqp_nmpc_stage_qp.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int, C.POINTER(NmpcData)] + \
         [_PD] * 11
     lib.bqp_nmpc_stage_qp_device.argtypes = lib.bqp_nmpc_stage_qp.argtypes + [C.c_void_p]
+    lib.bqp_nmpc_stage_cost.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int, C.POINTER(NmpcData)] + \
+        [_PD] * 3
     lib.bqp_nmpc_solve_batched.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int,
                                            C.POINTER(NmpcData), C.POINTER(Options), _PD, _PD, _PD,
                                            _PI, _PI]

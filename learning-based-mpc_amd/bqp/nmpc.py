@@ -63,9 +63,16 @@ class NMPC:
     def _dims(self, subproblem='dense'):
         return _lib.NmpcDims(self.N, self.mx, self.mu, self.mp, _subproblem(subproblem))
 
-    def _data(self, x0=None):
+    def _data(self, x0=None, soft=(None, None)):
         return _lib.NmpcData(*[_lib.ptr(a) for a in self._keep], self.delta,
-                             _lib.ptr(x0) if x0 is not None else None, 4)
+                             _lib.ptr(x0) if x0 is not None else None, 4,
+                             *[_lib.ptr(a) if a is not None else None for a in soft])
+
+    def _soft(self, xs_lin, xs_quad):
+        """the row weights as the C structure takes them: None, or mx doubles (a scalar is every
+        row's weight).  The caller keeps the arrays alive over the call."""
+        return tuple(None if a is None else _f64(np.broadcast_to(np.asarray(a, float), (self.mx,))).copy()
+                     for a in (xs_lin, xs_quad))
 
     def _z(self, b, z):
         if z is None:
@@ -113,16 +120,37 @@ class NMPC:
         return OcpResult(A=np.swapaxes(Acm, 2, 3), B=B, w=w, xlb=xlb, xub=xub, ulb=ulb, uub=uub, hp=hp,
                          W=np.swapaxes(W, 1, 2), Fp=Fcm.T)
 
+    def stage_cost(self, xmeasure, z=None, xs_lin=None, xs_quad=None, handle=None):
+        """what the stage route's merit function starts from at z (bqp_nmpc_stage_cost): cost
+        (batch,) = J + penalty and penalty (batch,), the penalty of the softened rows at z."""
+        lib = _lib.load()
+        h = handle or _default_handle()
+        x0 = _f64(np.atleast_2d(xmeasure))
+        b = x0.shape[0]
+        z = self._z(b, z)
+        cost = np.zeros(b); pen = np.zeros(b)
+        soft = self._soft(xs_lin, xs_quad)
+        dims, dd = self._dims('stage'), self._data(x0, soft)
+        rc = lib.bqp_nmpc_stage_cost(h.value, C.byref(dims), b, C.byref(dd), _lib.ptr(z), _lib.ptr(cost),
+                                     _lib.ptr(pen))
+        _lib.check(rc, 'bqp_nmpc_stage_cost')
+        return OcpResult(cost=cost, penalty=pen)
+
     def solve(self, xmeasure, y0=None, z0=None, handle=None, max_iter=100, tol=1e-8, polish=0,
-              subproblem='dense'):
+              subproblem='dense', xs_lin=None, xs_quad=None):
         """xmeasure (batch, 4) absolute states; y0 a start in the script's layout
         [x_0..x_N; u; theta] (its states are ignored: they follow from u) or z0 = [u - u_eq;
         theta]; cold start u = u_eq, theta = 0 otherwise.  subproblem: 'dense' (the condensed
         sub-problem on the dense kernels) or 'stage' (the sub-problem in stage form on the
         structured kernel with per-stage models; F_x and F_u must be box rows; polish is then that
-        solve's: 0 / 1 after a 0 / -8 exit, 2 also on weakly active rows, -1 off).  Returns y_OL
-        (batch, 4 (N + 1) + N + 1) in the script's layout, u0, theta, z, lam (batch, m), cost,
-        exitflag, iterations."""
+        solve's: 0 / 1 after a 0 / -8 exit, 2 also on weakly active rows, -1 off).  xs_lin, xs_quad:
+        soft state rows, a scalar or mx weights l1, l2 >= 0 per row of F_x (stage route only): a row
+        with a positive weight may be violated at the price l1 s + 0.5 l2 s^2 of its slack s; the
+        two rows of one state variable must carry the same weights in the variable's units
+        (bqp_nmpc_data in bqp.h).  Returns y_OL
+        (batch, 4 (N + 1) + N + 1) in the script's layout, u0, theta, z, lam (batch, m), cost (with
+        weights: J + penalty), exitflag, iterations, slack (batch, N, mx) = max(c, 0) on the
+        softened rows and 0 elsewhere, penalty (batch,)."""
         lib = _lib.load()
         h = handle or _default_handle()
         x0 = _f64(np.atleast_2d(xmeasure))
@@ -133,7 +161,8 @@ class NMPC:
         z = self._z(b, z0)
         lam = np.zeros((b, m)); cost = np.zeros(b)
         flag = np.zeros(b, np.int32); it = np.zeros(b, np.int32)
-        dims, dd = self._dims(subproblem), self._data(x0)
+        soft = self._soft(xs_lin, xs_quad)
+        dims, dd = self._dims(subproblem), self._data(x0, soft)
         o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
         rc = lib.bqp_nmpc_solve_batched(h.value, C.byref(dims), b, C.byref(dd), C.byref(o),
                                         _lib.ptr(z), _lib.ptr(lam), _lib.ptr(cost), _lib.iptr(flag),
@@ -141,22 +170,27 @@ class NMPC:
         _lib.check(rc, 'bqp_nmpc_solve_batched')
         r = OcpResult(z=z, lam=lam, cost=cost, exitflag=flag, iterations=it)
         # the open-loop states of the solution: the rollout the solver itself computes
-        X = np.zeros((b, N + 1, 4))
+        # and the rows' values there, for the slacks of the softened rows
+        X = np.zeros((b, N + 1, 4)); c = np.zeros((b, m))
         rc = lib.bqp_nmpc_linearize(h.value, C.byref(dims), b, C.byref(dd), _lib.ptr(z), _lib.ptr(X),
-                                    None, None, None, None, None)
+                                    None, _lib.ptr(c), None, None, None)
         _lib.check(rc, 'bqp_nmpc_linearize')
+        l1, l2 = [np.zeros(self.mx) if a is None else a for a in soft]
+        ms = self.mx + self.mu
+        slack = np.maximum(c[:, :N * ms].reshape(b, N, ms)[:, :, :self.mx], 0.0) * ((l1 > 0) | (l2 > 0))
+        r.update(slack=slack, penalty=(l1 * slack + 0.5 * l2 * slack ** 2).sum(axis=(1, 2)))
         r.update(y_OL=np.concatenate([X.reshape(b, -1), z[:, :N] + self.u_eq[0], z[:, N:]], axis=1),
                  u0=z[:, :1] + self.u_eq[0], theta=z[:, N:])
         return r
 
 
 def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, polish=0,
-                     subproblem='dense'):
+                     subproblem='dense', xs_lin=None, xs_quad=None):
     """Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states x_init
     (batch, 4), absolute: per step the solve at the measured state, the RK4 plant with u_0, and
     the warm start (z shifted one stage, last move repeated, theta kept).  Every instance advances
     at its own step (with BQP_NMPC_SYNC set in the environment: the whole batch step by step, same
-    results).  subproblem as in NMPC.solve.  Returns X (batch, steps + 1, 4), U (batch, steps), exitflag and iterations
+    results).  subproblem, xs_lin and xs_quad as in NMPC.solve.  Returns X (batch, steps + 1, 4), U (batch, steps), exitflag and iterations
     (batch, steps), kernel_ms, launches and rounds, the SQP rounds the loop launched."""
     lib = _lib.load()
     h = handle or _default_handle()
@@ -164,7 +198,8 @@ def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, p
     b, steps = xi.shape[0], int(steps)
     X = np.zeros((b, steps + 1, 4)); U = np.zeros((b, steps))
     fl = np.zeros((b, steps), np.int32); it = np.zeros((b, steps), np.int32)
-    dims, dd = prob._dims(subproblem), prob._data()
+    soft = prob._soft(xs_lin, xs_quad)
+    dims, dd = prob._dims(subproblem), prob._data(soft=soft)
     cl = ClosedLoop(_BQP_PLANT_MG_RK4, steps, prob.delta, _lib.ptr(prob.x_eq), _lib.ptr(prob.u_eq))
     o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
     rc = lib.bqp_closed_loop_nmpc(h.value, C.byref(dims), b, C.byref(dd), C.byref(o), C.byref(cl),

@@ -1538,6 +1538,24 @@ static void stage_nmpc_data(Stage& st, const bqp_nmpc_dims* d, const bqp_nmpc_da
     st.in(&Dd->F_x, D->F_x, 4 * mx);    st.in(&Dd->h_x, D->h_x, mx);
     st.in(&Dd->F_u, D->F_u, mu);        st.in(&Dd->h_u, D->h_u, mu);
     st.in(&Dd->F_T, D->F_T, 5 * mp);    st.in(&Dd->h_T, D->h_T, mp);
+    st.in(&Dd->xs_lin, D->xs_lin, mx);  st.in(&Dd->xs_quad, D->xs_quad, mx);
+}
+
+// soft state rows (bqp_nmpc_data.xs_lin / xs_quad): a weight array is given
+static bool nmpc_soft(const bqp_nmpc_data* D) { return D->xs_lin || D->xs_quad; }
+
+// the solve and loop entries: the soft rows exist on the stage route only
+static int nmpc_soft_check(const bqp_nmpc_dims* d, const bqp_nmpc_data* D) {
+    return (nmpc_soft(D) && d->subproblem != 1) ? BQP_E_UNSUPPORTED : BQP_OK;
+}
+
+// host entry points: every weight finite and >= 0 (the device entries leave that to the caller)
+static int nmpc_soft_host_check(const bqp_nmpc_dims* d, const bqp_nmpc_data* D) {
+    for (const double* w : {D->xs_lin, D->xs_quad})
+        if (w)
+            for (int i = 0; i < d->mx; ++i)
+                if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return BQP_E_ARG;
+    return BQP_OK;
 }
 
 // Stage route (bqp_nmpc_dims.subproblem = 1): the SQP's kernel arguments over the handle's nwork
@@ -1554,14 +1572,21 @@ struct NmpcStageRoute {
     bqp_options qo;
     double *xo, *uo, *tho, *fv;
     int* sflag;
+    // soft state rows: set where a weight is given and some row is softened by it (the table
+    // kernel's finding); otherwise every launch is the hard route's own
+    bool soft;
+    bqp::NmpcSoftArgs q;
+    const bqp::NmpcSoftArgs* softp() const { return soft ? &q : nullptr; }
 };
 
+// use_soft = false: the weights of D are not read (the diagnostic bqp_nmpc_stage_qp)
 static int nmpc_stage_setup(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
                             const bqp_options& o, hipStream_t st, NmpcStageRoute& R,
-                            const bqp::NmpcStageArgs* user = nullptr) {
+                            const bqp::NmpcStageArgs* user = nullptr, bool use_soft = true) {
     const int N = d->N, n = N + 1, mp = d->n_poly, m = N * (d->mx + d->mu) + mp;
     const size_t B = batch;
-    const layout::NworkStage NL(batch, N, mp, m, LB_NTRIAL, sizeof(bqp::NmpcBoundMap));
+    const bool want_soft = use_soft && nmpc_soft(D);
+    const layout::NworkStage NL(batch, N, mp, m, LB_NTRIAL, sizeof(bqp::NmpcBoundMap), want_soft ? 1 : 0);
     if (getenv("BQP_LB_TRACE"))
         fprintf(stderr, "bqp nmpc stage route: workspace %zu bytes for %d instances\n", NL.bytes, batch);
     HIP_TRY(h->nwork.reserve(NL.bytes));
@@ -1621,12 +1646,24 @@ static int nmpc_stage_setup(bqp_handle h, const bqp_nmpc_dims* d, int batch, con
     s.sflag = R.sflag;
     double* x0z = layout::at<double>(nw, NL.x0z);
     HIP_TRY(hipMemsetAsync(x0z, 0, sizeof(double) * 4, st));
-    // the shared tables and the bound map; one flag back: F_x, F_u must be box rows
-    HIP_TRY(bqp::launch_nmpc_stage_table(a, s, st));
-    int notbox = 0;
-    HIP_TRY(hipMemcpyAsync(&notbox, &s.map->notbox, sizeof(int), hipMemcpyDeviceToHost, st));
+    R.soft = false;
+    memset(&R.q, 0, sizeof(R.q));
+    if (want_soft) {
+        R.q.xs_lin = D->xs_lin; R.q.xs_quad = D->xs_quad;
+        R.q.xsl = layout::at<double>(nw, NL.xsl);
+        R.q.xsq = layout::at<double>(nw, NL.xsq);
+        R.q.sx = layout::at<double>(nw, NL.sx);
+        R.q.pen0 = layout::at<double>(nw, NL.pen0);
+        R.q.plin = layout::at<double>(nw, NL.plin);
+    }
+    // the shared tables and the bound map; the map back, in one copy: F_x, F_u must be box rows,
+    // and the softened rows must pair up as the structured solve's weights do
+    HIP_TRY(bqp::launch_nmpc_stage_table(a, s, st, want_soft ? &R.q : nullptr));
+    bqp::NmpcBoundMap hm;
+    HIP_TRY(hipMemcpyAsync(&hm, s.map, sizeof(hm), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (notbox) return BQP_E_UNSUPPORTED;
+    if (hm.notbox || hm.unsupported) return BQP_E_UNSUPPORTED;
+    R.soft = want_soft && hm.anysoft;
     memset(&R.od, 0, sizeof(R.od));
     R.od.nx = 4; R.od.nu = 1; R.od.np = 1; R.od.N = N; R.od.n_poly = mp; R.od.poly_stage = N;
     R.od.stage_models = 1;
@@ -1643,11 +1680,23 @@ static int nmpc_stage_setup(bqp_handle h, const bqp_nmpc_dims* d, int batch, con
     oD.hp = mp > 0 ? s.hp : nullptr; oD.shp = mp;
     oD.x0 = x0z; oD.sx0 = 0;
     oD.skip = a.done;
+    if (R.soft) {
+        // the structured solve's soft state bounds: the tables shared by the batch, the slacks back
+        oD.xs_lin = R.q.xsl; oD.xs_quad = R.q.xsq; oD.sxs = 0;
+        R.du.s_x = const_cast<double*>(R.q.sx);
+    }
     // the sub-problem's options: the structured solve's defaults with the dense sub-problem's
     // iteration limit; polish as the caller set it, in that solve's own encoding
     bqp_default_options(&R.qo);
     R.qo.max_iter = 100;
     R.qo.polish = o.polish;
+    // Soft sub-problems have no active-set polish: the interior point's own stationarity bounds
+    // the accuracy of the SQP's fixed point, so it follows the caller's tolerance, 1e-4 below it.
+    // Measured (N = 10, start 0.05 above the x2 bound, tol 1e-10): the first free move is 9e-9
+    // off the exact sub-problems' with the residual at 1e-13 (1 + |g|), 3e-10 at 1e-14.  A
+    // sub-problem that cannot reach it ends 0 / -8 on its last interior iterate, which the update
+    // kernel takes as is.
+    if (R.soft) R.qo.tol_stat = std::min(R.qo.tol_stat, 1e-4 * o.tol_stat);
     return BQP_OK;
 }
 
@@ -1663,17 +1712,17 @@ static int nmpc_stage_round(bqp_handle h, const NmpcStageRoute& R, hipStream_t s
         return BQP_OK;
     };
     BQP_TRY(mark(0));
-    HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st));
+    HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st, R.softp()));
     BQP_TRY(mark(1));
     BQP_TRY(bqp_solve_ocp_batched_device(h, &R.od, R.a.batch, &R.oD, &R.qo, R.xo, R.uo, R.tho, R.fv, R.sflag,
                                          nullptr, &R.du, st));
     *launches += h->launches;
     BQP_TRY(mark(2));
-    HIP_TRY(bqp::launch_nmpc_stage_backmap(R.a, R.s, st));
+    HIP_TRY(bqp::launch_nmpc_stage_backmap(R.a, R.s, st, R.softp()));
     BQP_TRY(mark(3));
-    HIP_TRY(bqp::launch_nmpc_rollout(R.a, 0, st));
+    HIP_TRY(bqp::launch_nmpc_rollout(R.a, 0, st, R.softp()));
     BQP_TRY(mark(4));
-    HIP_TRY(bqp::launch_nmpc_update(R.a, st));
+    HIP_TRY(bqp::launch_nmpc_update(R.a, st, R.softp()));
     BQP_TRY(mark(5));
     *launches += 4;
     return BQP_OK;
@@ -1753,10 +1802,41 @@ int bqp_nmpc_stage_qp_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     user.A = A; user.B = B; user.w = w; user.xlb = xlb; user.xub = xub; user.ulb = ulb; user.uub = uub;
     user.hp = hp; user.W = W; user.Fp = Fp;
     NmpcStageRoute R;
-    BQP_TRY(nmpc_stage_setup(h, d, batch, D, o, st, R, &user));
+    BQP_TRY(nmpc_stage_setup(h, d, batch, D, o, st, R, &user, false));
     R.a.z = const_cast<double*>(z);     // read only by the rollout
     HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st));
     return BQP_OK;
+}
+
+int bqp_nmpc_stage_cost(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                        const double* z, double* cost, double* penalty) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z) return BQP_E_ARG;
+    BQP_TRY(nmpc_soft_host_check(d, D));
+    if (bqp::ocp_rpl_for(std::max(d->n_poly, 1)) < 0) return BQP_E_UNSUPPORTED;
+    DevScope ds(h->device);
+    const size_t Bt = batch, N = d->N;
+    Stage st(h);
+    bqp_nmpc_data Dd;
+    const double* zd;
+    double *cd = nullptr, *pd = nullptr;
+    stage_nmpc_data(st, d, D, &Dd);
+    st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
+    st.in(&zd, z, Bt * (N + 1));
+    st.out(&cd, Bt, cost);
+    st.out(&pd, Bt, penalty);
+    BQP_TRY(st.commit());
+    bqp_options o;
+    resolve(nullptr, &o);
+    NmpcStageRoute R;
+    BQP_TRY(nmpc_stage_setup(h, d, batch, &Dd, o, h->stream, R));
+    R.a.z = const_cast<double*>(zd);    // read only by the rollout
+    HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, h->stream, R.softp()));
+    HIP_TRY(hipMemcpyAsync(cd, R.a.cost0, sizeof(double) * Bt, hipMemcpyDeviceToDevice, h->stream));
+    if (R.soft) HIP_TRY(hipMemcpyAsync(pd, R.q.pen0, sizeof(double) * Bt, hipMemcpyDeviceToDevice, h->stream));
+    else HIP_TRY(hipMemsetAsync(pd, 0, sizeof(double) * Bt, h->stream));
+    return st.finish();
 }
 
 int bqp_nmpc_stage_qp(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
@@ -1765,6 +1845,7 @@ int bqp_nmpc_stage_qp(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_check(d, batch, D, true));
     if (!z) return BQP_E_ARG;
+    BQP_TRY(nmpc_soft_host_check(d, D));
     DevScope ds(h->device);
     const size_t Bt = batch, N = d->N, mp = d->n_poly;
     Stage st(h);
@@ -1798,6 +1879,7 @@ int bqp_nmpc_linearize(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bq
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_check(d, batch, D, true));
     if (!z) return BQP_E_ARG;
+    BQP_TRY(nmpc_soft_host_check(d, D));
     DevScope ds(h->device);
     const size_t B = batch, N = d->N, n = N + 1, m = N * (size_t)(d->mx + d->mu) + d->n_poly;
     Stage st(h);
@@ -1825,6 +1907,7 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_check(d, batch, D, true));
     if (!z || !exitflag || !iterations) return BQP_E_ARG;
+    BQP_TRY(nmpc_soft_check(d, D));
     DevScope ds(h->device);
     hipStream_t st = (hipStream_t)stream;
     bqp_options o;
@@ -1920,6 +2003,8 @@ int bqp_nmpc_solve_batched(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_check(d, batch, D, true));
     if (!z || !exitflag || !iterations) return BQP_E_ARG;
+    BQP_TRY(nmpc_soft_host_check(d, D));
+    BQP_TRY(nmpc_soft_check(d, D));
     DevScope ds(h->device);
     const size_t B = batch, N = d->N, n = N + 1, m = N * (size_t)(d->mx + d->mu) + d->n_poly;
     Stage st(h);
@@ -1946,7 +2031,7 @@ static int nmpc_loop_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_dat
     if (cl->plant != BQP_PLANT_MG_RK4 || cl->steps < 0 || !(cl->delta > 0) || !cl->x_eq || !cl->u_eq ||
         (cl->steps > 0 && !U))
         return BQP_E_ARG;
-    return BQP_OK;
+    return nmpc_soft_check(d, D);
 }
 
 int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
@@ -2066,6 +2151,7 @@ int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const 
                          double* X, double* U, int* exitflag, int* iterations) {
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_loop_check(d, batch, D, cl, x_init, X, U));
+    BQP_TRY(nmpc_soft_host_check(d, D));
     DevScope ds(h->device);
     const size_t B = batch, S = cl->steps;
     Stage st(h);

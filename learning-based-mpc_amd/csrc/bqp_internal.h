@@ -204,16 +204,32 @@ struct NmpcStageArgs {
     const double *uo, *tho, *lamx, *lamu, *lamp;     // the solve's u, theta and multipliers
     const int* sflag;                                // and exit flags
 };
+// Soft state rows of the stage route (bqp_nmpc_data.xs_lin / xs_quad).  A separate, trailing kernel
+// argument: NmpcArgs and NmpcStageArgs keep their layout, so the hard instantiations read their
+// arguments where they always did.  The launchers take a null pointer for "every row hard".
+struct NmpcSoftArgs {
+    const double *xs_lin, *xs_quad;   // shared: mx row weights each, either may be null (zeros)
+    double *xsl, *xsq;                // shared: (N+1) x 4, the structured solve's xs_lin / xs_quad
+    const double* sx;                 // batch x 8 (N+1): the structured solve's s_x
+    double *pen0, *plin;              // batch each: the penalty at z, the sub-problem's model penalty
+};
 bool nmpc_supported(int N, int mx, int mu);
-// stage route: the shared tables (W, Fp, bound map), once per solve
-hipError_t launch_nmpc_stage_table(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st);
-// the rollout at z with the stage Jacobians: A, B, w, bounds, hp, rhs, cost0
-hipError_t launch_nmpc_stage_rollout(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st);
+// stage route: the shared tables (W, Fp, bound map; with q also the weight tables), once per solve
+hipError_t launch_nmpc_stage_table(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
+                                   const NmpcSoftArgs* q = nullptr);
+// the rollout at z with the stage Jacobians: A, B, w, bounds, hp, rhs, cost0 (with q: pen0, and
+// cost0 = J + pen0)
+hipError_t launch_nmpc_stage_rollout(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
+                                     const NmpcSoftArgs* q = nullptr);
 // after the structured solve: d, lam in NMPC row order, qpflag, f and C'lam by the adjoint sweep
-hipError_t launch_nmpc_stage_backmap(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st);
+// (with q: plin from the solve's slacks)
+hipError_t launch_nmpc_stage_backmap(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
+                                     const NmpcSoftArgs* q = nullptr);
 // gn = 1: rollout with sensitivities at z (Jr, er, C, rhs, cost0); gn = 0: the ntrial trial points
-hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st);
-hipError_t launch_nmpc_update(const NmpcArgs& a, hipStream_t st);
+// (with q: costT = J + penalty, violT over the hard rows)
+hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st, const NmpcSoftArgs* q = nullptr);
+// with q (stage route only): the hard rows' reductions and D = f'd + plin - pen0 - nu V0
+hipError_t launch_nmpc_update(const NmpcArgs& a, hipStream_t st, const NmpcSoftArgs* q = nullptr);
 // closed loop: after the plant step of step t, the step's SQP iteration counts into the log and
 // the warm start (z shifted one stage, last move repeated, theta kept)
 hipError_t launch_nmpc_loop_shift(int batch, int N, int steps, int t, double* z, const int* it,

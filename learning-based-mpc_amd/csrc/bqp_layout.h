@@ -142,9 +142,11 @@ struct NworkStage : Arena {
     size_t n;
     Region A, B, w, xlb, xub, ulb, uub, hp, xo, uo, tho, fv, lamx, lamu, lamp;
     Region rhs, lam, d, f, ctl, cost0, costT, violT, stat, cprev, nu;
+    Region xsl, xsq, sx, pen0, plin;   // soft state rows (soft = 1); empty otherwise
     Region W, Fp, x0z, map;
     Region sflag, qpflag, done, ndone;
-    NworkStage(size_t Bt, size_t N, size_t mp, size_t m, size_t ntrial, size_t map_bytes) : n(N + 1) {
+    NworkStage(size_t Bt, size_t N, size_t mp, size_t m, size_t ntrial, size_t map_bytes, size_t soft = 0)
+        : n(N + 1) {
         A = take<double>(Bt * N * 16);
         B = take<double>(Bt * N * 4);
         w = take<double>(Bt * (N + 1) * 6);
@@ -171,6 +173,13 @@ struct NworkStage : Arena {
         stat = take<double>(Bt);
         cprev = take<double>(Bt);
         nu = take<double>(Bt);
+        // the structured solve's shared weight tables and its slacks s_x, the penalty at the
+        // iterate and the sub-problem's model penalty
+        xsl = take<double>(soft * (N + 1) * 4);
+        xsq = take<double>(soft * (N + 1) * 4);
+        sx = take<double>(soft * Bt * (N + 1) * 8);
+        pen0 = take<double>(soft * Bt);
+        plin = take<double>(soft * Bt);
         W = take<double>((N + 1) * 36);
         Fp = take<double>(mp * 6);
         x0z = take<double>(4);

@@ -149,8 +149,12 @@ __device__ __forceinline__ void nm_load_consts(const NmpcArgs& a, int lane, doub
     }
 }
 
-template <bool GN>
-__global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a) {
+// SOFT (trial points of the stage route only): lane i < mx owns row i of F_x with its weights; a
+// softened row's max(c, 0) goes into the lane's penalty instead of V, costT = J + sum of the
+// penalties.  q is read by the SOFT instantiation alone.
+template <bool GN, bool SOFT = false>
+__global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a, NmpcSoftArgs q) {
+    static_assert(!(GN && SOFT), "the soft rows belong to the stage route: no linearisation here");
     const int lane = threadIdx.x;
     const int nt = GN ? 1 : a.ntrial;
     const int b = blockIdx.x / nt, t = blockIdx.x % nt;
@@ -189,6 +193,16 @@ __global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a) {
     double* Xout = (GN && a.Xout) ? a.Xout + (int64_t)b * (N + 1) * 4 : nullptr;
     double J = 0.0, V = 0.0;
     int row = 0;
+    // SOFT: the lane's row weights, the wave's mask of softened rows, the lane's penalty
+    double wl1 = 0.0, wl2 = 0.0, pen = 0.0;
+    unsigned long long softmask = 0;
+    if constexpr (SOFT) {
+        if (lane < mx) {
+            wl1 = q.xs_lin ? q.xs_lin[lane] : 0.0;
+            wl2 = q.xs_quad ? q.xs_quad[lane] : 0.0;
+        }
+        softmask = __ballot(wl1 > 0.0 || wl2 > 0.0);
+    }
     // weighted residual block L (v - LAMBDA theta) on the deviation v = x - x_eq, L upper
     // triangular 4 x 4 row-major at cst[oL]; GN: its Jacobian rows from the sensitivities
     auto xresidual = [&](int oL, const double (&xx)[4]) __attribute__((always_inline)) {
@@ -269,7 +283,12 @@ __global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a) {
             } else {
                 cv = cst[NO_FU + i - mx] * vk - cst[NO_HU + i - mx];
             }
-            V += fmax(cv, 0.0);
+            if constexpr (SOFT) {
+                if ((softmask >> i) & 1) { if (lane == i) pen += nmpc_phi(wl1, wl2, fmax(cv, 0.0)); }
+                else V += fmax(cv, 0.0);
+            } else {
+                V += fmax(cv, 0.0);
+            }
             if (GN) {
                 if (lane == 0) {
                     rhs[r0 + i] = -cv;
@@ -346,6 +365,7 @@ __global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a) {
         }
     }
     if (!GN) V += wsum(Vt);
+    if constexpr (SOFT) J += wsum(pen);
     if (lane == 0) {
         if (GN) {
             a.cost0[b] = J;
@@ -360,8 +380,12 @@ __global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a) {
 // convergence test + penalty + L1 merit line search + step (one wave per instance)
 // ------------------------------------------------------------------------------------------
 // STAGE: C'lam is the back-map's ready n-vector a.ctl (stage route), not the product over C
-template <bool STAGE>
-__global__ void __launch_bounds__(64) nmpc_update_kernel(NmpcArgs a) {
+// SOFT (stage route): the merit function is J + P + nu V with the penalty P of the softened rows in
+// the cost (cost0, costT) and V, the feasibility test and the multiplier bound of nu over the hard
+// rows alone; D = f'd + plin - pen0 - nu V0 with the sub-problem's model penalty plin
+template <bool STAGE, bool SOFT = false>
+__global__ void __launch_bounds__(64) nmpc_update_kernel(NmpcArgs a, NmpcSoftArgs q) {
+    static_assert(STAGE || !SOFT, "the soft rows belong to the stage route");
     const int b = blockIdx.x;
     const int lane = threadIdx.x;
     if (b >= a.batch || a.done[b]) return;
@@ -405,6 +429,12 @@ __global__ void __launch_bounds__(64) nmpc_update_kernel(NmpcArgs a) {
         sl += f[j] * d[j];
     }
     for (int r = lane; r < m; r += NM_WAVE) {
+        if constexpr (SOFT) {
+            const int ms = a.mx + a.mu, i = r % ms;
+            if (r < ms * a.N && i < a.mx &&
+                ((q.xs_lin && q.xs_lin[i] > 0.0) || (q.xs_quad && q.xs_quad[i] > 0.0)))
+                continue;
+        }
         const double cv = -rhs[r];
         viol = fmax(viol, cv);
         V0 += fmax(cv, 0.0);
@@ -432,7 +462,9 @@ __global__ void __launch_bounds__(64) nmpc_update_kernel(NmpcArgs a) {
     if (!fin) {
         // penalty of the L1 merit function phi = J + nu V, kept within the solve
         const double nu = fmax(a.nu[b], 1.1 * lmax);
-        const double D = sl - nu * V0, phi0 = J0 + nu * V0;
+        double D = sl - nu * V0;
+        if constexpr (SOFT) D = sl + q.plin[b] - q.pen0[b] - nu * V0;
+        const double phi0 = J0 + nu * V0;
         int tsel = a.ntrial - 1;
         for (int t = 0; t < a.ntrial; ++t) {
             const double al = ldexp(1.0, -t);
@@ -554,8 +586,10 @@ __device__ inline double nm_wentry(const double* L, const double* Lt, double lr,
 
 // once per solve: the shared cost blocks W ((N + 1) x 36), the polytope matrix
 // Fp = [F_T[:, :4] | 0 | F_T[:, 4]] (mp x 6, column-major) and the bound map of F_x, F_u with its
-// "not a box" flag
-__global__ void __launch_bounds__(64) nmpc_stage_table_kernel(NmpcArgs a, NmpcStageArgs s) {
+// "not a box" flag; the map's soft members from the row weights (all hard without them) and, where
+// q.xsl is set, the structured solve's weight tables xs_lin / xs_quad ((N + 1) x 4, shared by the
+// batch; stage 0 is not read): the pair of the variable's softened row, 0 for a hard variable
+__global__ void __launch_bounds__(64) nmpc_stage_table_kernel(NmpcArgs a, NmpcStageArgs s, NmpcSoftArgs q) {
     const int lane = threadIdx.x, N = a.N, mp = a.mp;
     for (int i = lane; i < 36 * (N + 1); i += NM_WAVE) {
         const int blk = i / 36, e = i % 36;
@@ -566,28 +600,47 @@ __global__ void __launch_bounds__(64) nmpc_stage_table_kernel(NmpcArgs a, NmpcSt
         const int c = i / mp, r = i % mp;
         s.Fp[i] = c < 4 ? a.FT[r + (int64_t)mp * c] : (c == 4 ? 0.0 : a.FT[r + (int64_t)mp * 4]);
     }
-    if (lane == 0) nmpc_bound_map_build(a.Fx, a.mx, a.Fu, a.mu, s.map);
+    if (lane == 0) {
+        nmpc_bound_map_build(a.Fx, a.mx, a.Fu, a.mu, s.map);
+        nmpc_bound_map_soften(s.map, a.mx, q.xs_lin, q.xs_quad);
+    }
+    if (q.xsl) {                     // uniform over the block
+        __syncthreads();             // lane 0's map
+        for (int i = lane; i < 4 * (N + 1); i += NM_WAVE) {
+            double lin, quad;
+            nmpc_var_pair(*s.map, i & 3, &lin, &quad);
+            q.xsl[i] = i < 4 ? 0.0 : lin;
+            q.xsq[i] = i < 4 ? 0.0 : quad;
+        }
+    }
 }
 
 // the bound map into LDS, lanes over its words (the caller syncs the wave)
-__device__ __forceinline__ void nm_load_map(const NmpcBoundMap* g, int lane, NmpcBoundMap* l) {
-    static_assert(sizeof(NmpcBoundMap) % sizeof(int) == 0, "copied by ints");
-    for (int i = lane; i < (int)(sizeof(NmpcBoundMap) / sizeof(int)); i += NM_WAVE)
-        ((int*)l)[i] = ((const int*)g)[i];
+// Map = NmpcBoundBox (the hard route: the box part alone) or NmpcBoundMap
+template <class Map>
+__device__ __forceinline__ void nm_load_map(const NmpcBoundMap* g, int lane, Map* l) {
+    static_assert(sizeof(Map) % sizeof(int) == 0, "copied by ints");
+    for (int i = lane; i < (int)(sizeof(Map) / sizeof(int)); i += NM_WAVE)
+        ((int*)l)[i] = ((const int*)static_cast<const Map*>(g))[i];
 }
+template <bool SOFT> struct NmMapOf { typedef NmpcBoundBox type; };
+template <> struct NmMapOf<true> { typedef NmpcBoundMap type; };
 
 // The third mode of the rollout, one wave per instance: nm_rk4<true> from the measured state
 // without sensitivities - the rollout and the stage Jacobians are the operation sequence of
 // nmpc_rollout_kernel<true>.  Every lane carries the rollout (the work per stage is wave-uniform);
 // lanes 0..25 store the stage's A_k | B_k | w_k, lanes i < mx + mu the value of row i of the next
 // stage (rhs = -c) and the bound it stands for, lanes over the rows of F_T the terminal rhs and hp.
-__global__ void __launch_bounds__(64) nmpc_stage_rollout_kernel(NmpcArgs a, NmpcStageArgs s) {
+// SOFT: lane i < mx also sums its row's penalty phi_i(max(c, 0)) over the stages; one wave sum gives
+// pen0, and cost0 = J + pen0.  The bounds stay as they are: the structured solve softens them.
+template <bool SOFT>
+__global__ void __launch_bounds__(64) nmpc_stage_rollout_kernel(NmpcArgs a, NmpcStageArgs s, NmpcSoftArgs q) {
     const int lane = threadIdx.x, b = blockIdx.x;
     if (b >= a.batch || a.done[b]) return;
     const int N = a.N, n = a.n, m = a.m, mx = a.mx, mu = a.mu, ms = mx + mu, mp = a.mp;
     __shared__ double zsh[NM_WAVE * NM_CPL];
     __shared__ double cst[NO_END];
-    __shared__ NmpcBoundMap map;
+    __shared__ typename NmMapOf<SOFT>::type map;
     {
         const double* z = a.z + (int64_t)b * n;
         for (int j = lane; j < n; j += NM_WAVE) zsh[j] = z[j];
@@ -632,6 +685,7 @@ __global__ void __launch_bounds__(64) nmpc_stage_rollout_kernel(NmpcArgs a, Nmpc
         bstride = isx ? 4 : 1;
     }
     double J = 0.0;
+    double pen = 0.0;                // SOFT: the lane's row's penalty over the stages
     // weighted residual e = L (xx - x_eq - LAMBDA theta) as nmpc_rollout_kernel's xresidual forms
     // it, and the x block of the stage gradient 2 L'e
     auto xgrad = [&](int oL, const double (&xx)[4], double (&wx)[4]) __attribute__((always_inline)) {
@@ -695,6 +749,9 @@ __global__ void __launch_bounds__(64) nmpc_stage_rollout_kernel(NmpcArgs a, Nmpc
             }
             rhs[nmpc_stage_row(mx, mu, k + 1, lane)] = -cv;
             bnd[(int64_t)k * bstride] = nmpc_bound_value(map, lane, -cv);
+            if constexpr (SOFT) {
+                if (lane < mx) pen += nmpc_phi(map.l1[lane], map.l2[lane], fmax(cv, 0.0));
+            }
         }
     }
     // terminal P on x_N, T on LAMBDA theta: w_N = [2 Lp'e; 0; -LAMBDA'(2 Lp'e) + 2 (Lt LAMBDA)'(Lt LAMBDA) theta]
@@ -730,7 +787,12 @@ __global__ void __launch_bounds__(64) nmpc_stage_rollout_kernel(NmpcArgs a, Nmpc
         rhs[rT + r] = -cv;
         hp[r] = -cv;
     }
-    if (lane == 0) a.cost0[b] = J;
+    if constexpr (SOFT) {
+        const double P0 = wsum(pen);
+        if (lane == 0) { q.pen0[b] = P0; a.cost0[b] = J + P0; }
+    } else {
+        if (lane == 0) a.cost0[b] = J;
+    }
 }
 
 // After the structured solve, one wave per instance (a finished instance leaves at once): the step
@@ -739,11 +801,15 @@ __global__ void __launch_bounds__(64) nmpc_stage_rollout_kernel(NmpcArgs a, Nmpc
 // w_k) and C'lam (from the multipliers) that nmpc_update_kernel<true> reads:
 //   p_N = x part (+ F_x'lam_N + F_T[:, :4]'lam_T),  g_k = u part + B_k'p_{k+1} (+ F_u lam),
 //   p_k = x part + A_k'p_{k+1} (+ F_x'lam_k),  theta entry = sum of the theta parts (+ F_T[:, 4]'lam_T)
-__global__ void __launch_bounds__(64) nmpc_stage_backmap_kernel(NmpcArgs a, NmpcStageArgs s) {
+// SOFT: a softened row's multiplier is that of the softened bound, lam_x / |a|, by the same map;
+// the structured solve's slacks s_x give the row slacks |a| s_x and the sub-problem's model penalty
+// plin = sum phi_i(|a| s_x), lanes over the rows, one wave sum.
+template <bool SOFT>
+__global__ void __launch_bounds__(64) nmpc_stage_backmap_kernel(NmpcArgs a, NmpcStageArgs s, NmpcSoftArgs q) {
     const int lane = threadIdx.x, b = blockIdx.x;
     if (b >= a.batch || a.done[b]) return;
     const int N = a.N, n = a.n, m = a.m, mx = a.mx, mu = a.mu, mp = a.mp;
-    __shared__ NmpcBoundMap map;
+    __shared__ typename NmMapOf<SOFT>::type map;
     __shared__ double gf[NM_WAVE * NM_CPL], gl[NM_WAVE * NM_CPL];
     nm_load_map(s.map, lane, &map);
     wave_sync();
@@ -759,6 +825,18 @@ __global__ void __launch_bounds__(64) nmpc_stage_backmap_kernel(NmpcArgs a, Nmpc
         a.qpflag[b] = s.sflag[b];
     }
     for (int r = lane; r < m; r += NM_WAVE) lam[r] = nmpc_stage_dual(map, N, mx, mu, r, lamx, lamu, lamp);
+    if constexpr (SOFT) {
+        const double* sx = q.sx + (int64_t)b * (N + 1) * 8;
+        const int ms = mx + mu;
+        double pl = 0.0;
+        for (int r = lane; r < ms * N; r += NM_WAVE) {
+            const int k = r / ms + 1, i = r % ms;
+            if (i < mx && map.soft[i])
+                pl += nmpc_phi(map.l1[i], map.l2[i], nmpc_row_slack(map, i, sx[nmpc_sx_index(map, k, i)]));
+        }
+        pl = wsum(pl);
+        if (lane == 0) q.plin[b] = pl;
+    }
     // F_T'lam_T: lanes over the rows, five wave sums
     double tT[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int r = lane; r < mp; r += NM_WAVE) {
@@ -837,25 +915,37 @@ static bool nmpc_stage_args_ok(const NmpcArgs& a) {
            a.n <= NM_WAVE * NM_CPL && a.mx + a.mu <= NM_WAVE && a.batch >= 1 && a.mp >= 0;
 }
 
-hipError_t launch_nmpc_stage_table(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st) {
-    if (!nmpc_stage_args_ok(a) || !s.W || !s.map || (a.mp > 0 && !s.Fp)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nmpc_stage_table_kernel, dim3(1), dim3(64), 0, st, a, s);
+// the soft arguments of a launch: complete (q given) or all null
+static const NmpcSoftArgs nm_hard = {};
+static bool nmpc_soft_args_ok(const NmpcSoftArgs* q) {
+    return !q || ((q->xs_lin || q->xs_quad) && q->xsl && q->xsq && q->sx && q->pen0 && q->plin);
+}
+
+hipError_t launch_nmpc_stage_table(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
+                                   const NmpcSoftArgs* q) {
+    if (!nmpc_stage_args_ok(a) || !s.W || !s.map || (a.mp > 0 && !s.Fp) || !nmpc_soft_args_ok(q))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_stage_table_kernel, dim3(1), dim3(64), 0, st, a, s, q ? *q : nm_hard);
     return hipGetLastError();
 }
 
-hipError_t launch_nmpc_stage_rollout(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st) {
+hipError_t launch_nmpc_stage_rollout(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
+                                     const NmpcSoftArgs* q) {
     if (!nmpc_stage_args_ok(a) || !s.A || !s.B || !s.w || !s.xlb || !s.xub || !s.ulb || !s.uub ||
-        (a.mp > 0 && !s.hp) || !s.map || !a.rhs || !a.cost0)
+        (a.mp > 0 && !s.hp) || !s.map || !a.rhs || !a.cost0 || !nmpc_soft_args_ok(q))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nmpc_stage_rollout_kernel, dim3(a.batch), dim3(64), 0, st, a, s);
+    if (q) hipLaunchKernelGGL(nmpc_stage_rollout_kernel<true>, dim3(a.batch), dim3(64), 0, st, a, s, *q);
+    else hipLaunchKernelGGL(nmpc_stage_rollout_kernel<false>, dim3(a.batch), dim3(64), 0, st, a, s, nm_hard);
     return hipGetLastError();
 }
 
-hipError_t launch_nmpc_stage_backmap(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st) {
+hipError_t launch_nmpc_stage_backmap(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
+                                     const NmpcSoftArgs* q) {
     if (!nmpc_stage_args_ok(a) || !s.uo || !s.tho || !s.lamx || !s.lamu || (a.mp > 0 && !s.lamp) ||
-        !s.sflag || !s.map || !a.ctl || !a.f || !a.d || !a.lam)
+        !s.sflag || !s.map || !a.ctl || !a.f || !a.d || !a.lam || !nmpc_soft_args_ok(q))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nmpc_stage_backmap_kernel, dim3(a.batch), dim3(64), 0, st, a, s);
+    if (q) hipLaunchKernelGGL(nmpc_stage_backmap_kernel<true>, dim3(a.batch), dim3(64), 0, st, a, s, *q);
+    else hipLaunchKernelGGL(nmpc_stage_backmap_kernel<false>, dim3(a.batch), dim3(64), 0, st, a, s, nm_hard);
     return hipGetLastError();
 }
 
@@ -864,19 +954,21 @@ bool nmpc_supported(int N, int mx, int mu) {
            mu >= 0 && mu <= NMPC_MAXMU;
 }
 
-hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st) {
+hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st, const NmpcSoftArgs* q) {
     if (!nmpc_supported(a.N, a.mx, a.mu) || a.n != a.N + 1 || a.nr != 5 * a.N + 8 ||
-        a.m != a.N * (a.mx + a.mu) + a.mp)
+        a.m != a.N * (a.mx + a.mu) + a.mp || (q && (gn || !nmpc_soft_args_ok(q))))
         return hipErrorInvalidValue;
-    if (gn) hipLaunchKernelGGL(nmpc_rollout_kernel<true>, dim3(a.batch), dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(nmpc_rollout_kernel<false>, dim3(a.batch * a.ntrial), dim3(64), 0, st, a);
+    if (gn) hipLaunchKernelGGL((nmpc_rollout_kernel<true>), dim3(a.batch), dim3(64), 0, st, a, nm_hard);
+    else if (q) hipLaunchKernelGGL((nmpc_rollout_kernel<false, true>), dim3(a.batch * a.ntrial), dim3(64), 0, st, a, *q);
+    else hipLaunchKernelGGL((nmpc_rollout_kernel<false>), dim3(a.batch * a.ntrial), dim3(64), 0, st, a, nm_hard);
     return hipGetLastError();
 }
 
-hipError_t launch_nmpc_update(const NmpcArgs& a, hipStream_t st) {
-    if (a.n > NM_WAVE * NM_CPL) return hipErrorInvalidValue;
-    if (a.C) hipLaunchKernelGGL(nmpc_update_kernel<false>, dim3(a.batch), dim3(64), 0, st, a);
-    else if (a.ctl) hipLaunchKernelGGL(nmpc_update_kernel<true>, dim3(a.batch), dim3(64), 0, st, a);
+hipError_t launch_nmpc_update(const NmpcArgs& a, hipStream_t st, const NmpcSoftArgs* q) {
+    if (a.n > NM_WAVE * NM_CPL || (q && (a.C || !nmpc_soft_args_ok(q)))) return hipErrorInvalidValue;
+    if (a.C) hipLaunchKernelGGL((nmpc_update_kernel<false>), dim3(a.batch), dim3(64), 0, st, a, nm_hard);
+    else if (a.ctl && q) hipLaunchKernelGGL((nmpc_update_kernel<true, true>), dim3(a.batch), dim3(64), 0, st, a, *q);
+    else if (a.ctl) hipLaunchKernelGGL((nmpc_update_kernel<true>), dim3(a.batch), dim3(64), 0, st, a, nm_hard);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }

@@ -70,7 +70,10 @@ def main():
     ap.add_argument('--subproblem', choices=('dense', 'stage'), default='dense')
     ap.add_argument('--polish', type=int, default=0)
     ap.add_argument('--dump', default=None)
+    ap.add_argument('--soft', type=float, nargs=2, metavar=('L1', 'L2'), default=None,
+                    help='soft state rows in the closed loop: the weights on all rows of F_x (stage route)')
     a = ap.parse_args()
+    soft = dict(xs_lin=a.soft[0], xs_quad=a.soft[1]) if a.soft else {}
     if a.child:
         return child(a.batch, a.subproblem, a.polish)
     import torch
@@ -111,10 +114,11 @@ def main():
             os.environ['BQP_NMPC_SYNC'] = '1'
         try:
             if a.warmup:
-                bqp.closed_loop_nmpc(g, xi, 2, handle=h, subproblem=a.subproblem, polish=a.polish)
-            r = bqp.closed_loop_nmpc(g, xi, a.steps, handle=h, subproblem=a.subproblem, polish=a.polish)
+                bqp.closed_loop_nmpc(g, xi, 2, handle=h, subproblem=a.subproblem, polish=a.polish, **soft)
+            r = bqp.closed_loop_nmpc(g, xi, a.steps, handle=h, subproblem=a.subproblem, polish=a.polish, **soft)
         finally:
             os.environ.pop('BQP_NMPC_SYNC', None)
+        out.update(loop_soft=a.soft, loop_infeasible=int((r.exitflag == -2).sum()))
         out.update(loop_mode='sync' if a.sync else 'async', loop_steps=a.steps, loop_ms=r.kernel_ms,
                    loop_rounds=r.rounds,
                    loop_rounds_from_logs=int((r.iterations + (r.exitflag != 0)).sum(axis=1).max()),
