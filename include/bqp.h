@@ -311,6 +311,41 @@ int bqp_lbmpc_solve_batched_device(bqp_handle h, const bqp_lbmpc_dims* d, int ba
                                    double* lam, double* cost, int* exitflag, int* iterations,
                                    void* stream);
 
+/* The SQP's model at a given z (batch*n, read only), for tests and diagnostics: the launches of
+ * one SQP iteration that form the QP sub-problem (rollout with sensitivities, normal equations,
+ * with d->hessian = 1 and n <= 127 the exact-Hessian kernel) and, with dstep (batch*n, may be
+ * NULL), the line search's trial rollouts; neither the QP solve nor the update runs.  Every
+ * output may be NULL:
+ *   cost  (batch)         the cost at z
+ *   Jr    (batch*nr*n)    residual Jacobian, row-major nr x n per instance,
+ *                         nr = n_run (nx + nu) + 2 nx.  Row order: per running stage k < n_run
+ *                         the nx rows Lq (x^L_k - LAMBDA th), then the nu rows Lr (u^L_k - PSI th);
+ *                         then the nx rows Lp (x^T_N - LAMBDA th); then the nx rows
+ *                         Lt (LAMBDA th - xs).  cost = |er|^2
+ *   er    (batch*nr)      the residuals, in the same order
+ *   H     (batch*n*n)     the QP sub-problem's Hessian, n x n per instance with BOTH triangles
+ *                         written and exactly symmetric (so row- and column-major coincide).
+ *                         hused = 0: the Gauss-Newton 2 Jr'Jr.  hused = 1: the exact one,
+ *                         2 Jr'Jr + sum_k Xi_k' W_k Xi_k, plus the grid shift 1e-12 hd 4^k on its
+ *                         diagonal where it needed one to be positive definite (hd = max|H_ii|)
+ *   f     (batch*n)       gradient 2 Jr'er
+ *   rhs   (batch*m)       bin - Ain z
+ *   hused (batch)         1 where H is the exact Hessian; 0 with d->hessian = 0, with n > 127
+ *                         (silently Gauss-Newton), or where no grid shift made it definite
+ *   Jr2, Tr2 (batch*3N*n) row-major 3N x n per instance, rows 3k..3k+2: Xi_k = d[x_1; x_2; u]_k/dz
+ *                         and W_k Xi_k (W_k = sum_i p_{k+1,i} d2g_i).  Written only where the
+ *                         exact-Hessian kernel runs (d->hessian = 1 and n <= 127)
+ *   costT (batch*8)       the cost at z + 2^-t dstep, t = 0..7.  Written only with dstep */
+int bqp_lbmpc_linearize(bqp_handle h, const bqp_lbmpc_dims* d, int batch, const bqp_lbmpc_data* data,
+                        const double* z, const double* dstep, double* cost, double* Jr, double* er,
+                        double* H, double* f, double* rhs, int* hused, double* Jr2, double* Tr2,
+                        double* costT);
+int bqp_lbmpc_linearize_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
+                               const bqp_lbmpc_data* data, const double* z, const double* dstep,
+                               double* cost, double* Jr, double* er, double* H, double* f,
+                               double* rhs, int* hused, double* Jr2, double* Tr2, double* costT,
+                               void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Closed-loop simulation: per time step, the batched structured solve at
  * the measured states, then one step of the true plant with the first input - the loop of

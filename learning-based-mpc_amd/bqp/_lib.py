@@ -99,7 +99,7 @@ EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'b
            'bqp_nmpc_linearize', 'bqp_nmpc_linearize_device', 'bqp_nmpc_solve_batched',
            'bqp_nmpc_solve_batched_device', 'bqp_closed_loop_nmpc', 'bqp_closed_loop_nmpc_device',
            'bqp_last_loop_rounds', 'bqp_nmpc_stage_qp', 'bqp_nmpc_stage_qp_device',
-           'bqp_nmpc_stage_cost']
+           'bqp_nmpc_stage_cost', 'bqp_lbmpc_linearize', 'bqp_lbmpc_linearize_device']
 
 _lib = None
 
@@ -146,6 +146,10 @@ def load():
     lib.bqp_lbmpc_solve_batched_device.argtypes = [C.c_void_p, C.POINTER(LbmpcDims), C.c_int,
                                                    C.POINTER(LbmpcData), C.POINTER(Options), _PD,
                                                    _PD, _PD, _PI, _PI, C.c_void_p]
+    # z, dstep, cost, Jr, er, H, f, rhs, hused, Jr2, Tr2, costT
+    lib.bqp_lbmpc_linearize.argtypes = [C.c_void_p, C.POINTER(LbmpcDims), C.c_int,
+                                        C.POINTER(LbmpcData)] + [_PD] * 8 + [_PI] + [_PD] * 3
+    lib.bqp_lbmpc_linearize_device.argtypes = lib.bqp_lbmpc_linearize.argtypes + [C.c_void_p]
     lib.bqp_closed_loop_ocp.argtypes = [C.c_void_p, C.POINTER(OcpDims), C.c_int, C.POINTER(OcpData),
                                         C.POINTER(Options), C.c_void_p, _PD, _PD, _PD, _PI]
     lib.bqp_closed_loop_ocp_device.argtypes = [C.c_void_p, C.POINTER(OcpDims), C.c_int,

@@ -118,19 +118,15 @@ class _LearnedOCP:
         self.Bx = np.vstack(rx)
         self.Ain_cm = np.ascontiguousarray(self.Ain.T)             # column-major m x nz
 
-    def _solve(self, x0, data, z0, handle, max_iter, tol, polish=0):
-        lib = _lib.load()
-        h = handle or _default_handle()
+    def _marshal(self, x0, data):
+        """the C structs of one call at the states x0 (deviation coordinates) with the window data:
+        dims, data, batch and the arrays the structs point into (to be kept alive over the call)"""
         x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
         b = x0.shape[0]
         w, sd = _window(data)
         q, mask = w.shape[-2], int(w.shape[-1] == 8)
         bin_ = np.ascontiguousarray(self.b0[None, :] + x0 @ self.Bx.T)
         mrows = self.Ain.shape[0]
-        z = np.zeros((b, self.nz)) if z0 is None else \
-            np.ascontiguousarray(np.broadcast_to(np.atleast_2d(z0), (b, self.nz)), dtype=np.float64).copy()
-        lam = np.zeros((b, mrows)); cost = np.zeros(b)
-        flag = np.zeros(b, np.int32); it = np.zeros(b, np.int32)
         keep = [np.ascontiguousarray(a, dtype=np.float64) for a in
                 (self.A.T, self.B.T, self.K.T, self.Lq, self.Lr, self.Lp, self.Lt,
                  self.LAMBDA.T, self.PSI.T, self.xs)]
@@ -138,12 +134,64 @@ class _LearnedOCP:
                               mrows, mask, int(self.hessian == 'exact'))
         dd = _lib.LbmpcData(*[_lib.ptr(a) for a in keep], _lib.ptr(w), sd, _lib.ptr(x0), self.n,
                             _lib.ptr(self.Ain_cm), _lib.ptr(bin_), mrows, self.bandwidth, self.lam)
+        return dims, dd, b, keep + [w, x0, bin_]
+
+    def _solve(self, x0, data, z0, handle, max_iter, tol, polish=0):
+        lib = _lib.load()
+        h = handle or _default_handle()
+        dims, dd, b, keep = self._marshal(x0, data)
+        mrows = self.Ain.shape[0]
+        z = np.zeros((b, self.nz)) if z0 is None else \
+            np.ascontiguousarray(np.broadcast_to(np.atleast_2d(z0), (b, self.nz)), dtype=np.float64).copy()
+        lam = np.zeros((b, mrows)); cost = np.zeros(b)
+        flag = np.zeros(b, np.int32); it = np.zeros(b, np.int32)
         o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
         rc = lib.bqp_lbmpc_solve_batched(h.value, C.byref(dims), b, C.byref(dd), C.byref(o),
                                          _lib.ptr(z), _lib.ptr(lam), _lib.ptr(cost),
                                          _lib.iptr(flag), _lib.iptr(it))
         _lib.check(rc, 'bqp_lbmpc_solve_batched')
         return OcpResult(z=z, lam=lam, cost=cost, exitflag=flag, iterations=it)
+
+    # outputs of bqp_lbmpc_linearize in the order of its arguments (include/bqp.h)
+    LINEARIZE_OUTPUTS = ('cost', 'Jr', 'er', 'H', 'f', 'rhs', 'hused', 'Jr2', 'Tr2', 'costT')
+
+    def linearize_shapes(self, b):
+        """shapes of bqp_lbmpc_linearize's outputs for a batch of b"""
+        n, N = self.nz, self.N
+        nr = self.n_run * (self.n + self.m) + 2 * self.n
+        return dict(cost=(b,), Jr=(b, nr, n), er=(b, nr), H=(b, n, n), f=(b, n),
+                    rhs=(b, self.Ain.shape[0]), hused=(b,), Jr2=(b, 3 * N, n), Tr2=(b, 3 * N, n),
+                    costT=(b, 8))
+
+    def _linearize_call(self, x0, data, z, d, handle, out):
+        """bqp_lbmpc_linearize with the arrays of out (name -> array, or None for a NULL argument);
+        returns the call's code"""
+        lib = _lib.load()
+        h = handle or _default_handle()
+        dims, dd, b, keep = self._marshal(x0, data)
+        z = np.ascontiguousarray(np.broadcast_to(np.atleast_2d(z), (b, self.nz)), dtype=np.float64)
+        d = None if d is None else \
+            np.ascontiguousarray(np.broadcast_to(np.atleast_2d(d), (b, self.nz)), dtype=np.float64)
+        args = [_lib.iptr(out.get(k)) if k == 'hused' else _lib.ptr(out.get(k))
+                for k in self.LINEARIZE_OUTPUTS]
+        return lib.bqp_lbmpc_linearize(h.value, C.byref(dims), b, C.byref(dd), _lib.ptr(z),
+                                       _lib.ptr(d), *args)
+
+    def linearize(self, x0, data, z, d=None, handle=None):
+        """The SQP's model at z (batch, N*m + p) for the states x0 (batch, n; deviation
+        coordinates) and the window data - what one SQP iteration hands to its QP sub-problem
+        (bqp_lbmpc_linearize; test access): cost, Jr, er, H, f, rhs, hused, with
+        hessian = 'exact' also Jr2 and Tr2 (NaN where the exact-Hessian kernel does not run),
+        with a step d also costT (batch, 8), the cost at z + 2^-t d."""
+        b = np.atleast_2d(x0).shape[0]
+        out = {k: (np.zeros(s, np.int32) if k == 'hused' else np.full(s, np.nan))
+               for k, s in self.linearize_shapes(b).items()}
+        if self.hessian != 'exact':
+            out['Jr2'] = out['Tr2'] = None
+        if d is None:
+            out['costT'] = None
+        _lib.check(self._linearize_call(x0, data, z, d, handle, out), 'bqp_lbmpc_linearize')
+        return OcpResult({k: v for k, v in out.items() if v is not None})
 
 
 class LBMPC(_LearnedOCP):

@@ -819,8 +819,9 @@ static hipError_t lbmpc_setup(bqp_handle h, const bqp_lbmpc_dims* d, int batch, 
     a.Ain = D->Ain; a.bin = D->bin; a.sbin = D->sbin;
     if ((e = hipMemsetAsync(a.done, 0, sizeof(int) * (B + 1), st)) != hipSuccess) return e;   // done[], ndone
     if ((e = hipMemsetAsync(a.hused, 0, sizeof(int) * B, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(a.iters, 0, sizeof(int) * B, st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(a.flag, 0, sizeof(int) * B, st)) != hipSuccess) return e;
+    // (null in bqp_lbmpc_linearize, which launches no kernel that reads them)
+    if (a.iters && (e = hipMemsetAsync(a.iters, 0, sizeof(int) * B, st)) != hipSuccess) return e;
+    if (a.flag && (e = hipMemsetAsync(a.flag, 0, sizeof(int) * B, st)) != hipSuccess) return e;
     // QP sub-problem (dense kernel): min 0.5 d'Hd + f'd  s.t.  Ain d <= bin - Ain z
     const int64_t wst = bqp::dense_work_doubles(n, m, 0);
     const layout::Dwork DL(wst, batch, bqp::STATS_W);
@@ -985,6 +986,95 @@ int bqp_lbmpc_solve_batched(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
     st.out(&itd, B, iterations);
     BQP_TRY(st.commit());
     BQP_TRY(bqp_lbmpc_solve_batched_device(h, d, batch, &Dd, opt, zd, ld, cd, ed, itd, h->stream));
+    return st.finish();
+}
+
+// the model's exact Hessian is formed: asked for and its LDS fits (lbmpc_setup's a.hess)
+static bool lbmpc_exact(const bqp_lbmpc_dims* d) {
+    return d->hessian && bqp::lbmpc_hess_fits(d->N * d->nu + d->np);
+}
+
+int bqp_lbmpc_linearize_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
+                               const bqp_lbmpc_data* D, const double* z, const double* dstep,
+                               double* cost, double* Jr, double* er, double* H, double* f,
+                               double* rhs, int* hused, double* Jr2, double* Tr2, double* costT,
+                               void* stream) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(lbmpc_check(d, batch, D));
+    if (!z) return BQP_E_ARG;
+    DevScope ds(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    bqp_options o;
+    resolve(nullptr, &o);
+    const size_t B = batch, n = (size_t)d->N * d->nu + d->np, m = d->m;
+    bqp::LbmpcArgs a;
+    bqp::DenseKernelArgs q;
+    HIP_TRY(lbmpc_setup(h, d, batch, D, o, const_cast<double*>(z), nullptr, nullptr, nullptr, st, a, q));
+    const size_t nr = a.nr, n2 = (size_t)3 * d->N * n;
+    // one SQP iteration's model launches at the caller's z (read only: no update kernel)
+    HIP_TRY(bqp::launch_lbmpc_rollout(a, 1, st));
+    HIP_TRY(bqp::launch_lbmpc_normal(a, st));
+    if (a.hess) HIP_TRY(bqp::launch_lbmpc_hess(a, st));
+    if (dstep) {
+        HIP_TRY(hipMemcpyAsync(a.d, dstep, sizeof(double) * B * n, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(bqp::launch_lbmpc_rollout(a, 0, st));
+    }
+    auto copy = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
+        return (dst && bytes) ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) : hipSuccess;
+    };
+    HIP_TRY(copy(cost, a.cost0, sizeof(double) * B));
+    HIP_TRY(copy(Jr, a.Jr, sizeof(double) * B * nr * n));
+    HIP_TRY(copy(er, a.er, sizeof(double) * B * nr));
+    HIP_TRY(copy(H, a.H, sizeof(double) * B * n * n));
+    HIP_TRY(copy(f, a.f, sizeof(double) * B * n));
+    HIP_TRY(copy(rhs, a.bsh, sizeof(double) * B * m));
+    HIP_TRY(copy(hused, a.hused, sizeof(int) * B));
+    if (a.hess) {
+        HIP_TRY(copy(Jr2, a.Jr2, sizeof(double) * B * n2));
+        HIP_TRY(copy(Tr2, a.Tr2, sizeof(double) * B * n2));
+    }
+    if (dstep) HIP_TRY(copy(costT, a.costT, sizeof(double) * B * LB_NTRIAL));
+    return BQP_OK;
+}
+
+int bqp_lbmpc_linearize(bqp_handle h, const bqp_lbmpc_dims* d, int batch, const bqp_lbmpc_data* D,
+                        const double* z, const double* dstep, double* cost, double* Jr, double* er,
+                        double* H, double* f, double* rhs, int* hused, double* Jr2, double* Tr2,
+                        double* costT) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(lbmpc_check(d, batch, D));
+    if (!z) return BQP_E_ARG;
+    DevScope ds(h->device);
+    const size_t B = batch, nx = d->nx, m = d->m, n = (size_t)d->N * d->nu + d->np;
+    const size_t nr = (size_t)d->n_run * (d->nx + d->nu) + 2 * nx, n2 = (size_t)3 * d->N * n;
+    const bool exact = lbmpc_exact(d);
+    Stage st(h);
+    bqp_lbmpc_data Dd;
+    const double *zd, *dd;
+    double *cd = nullptr, *Jd = nullptr, *ed = nullptr, *Hd = nullptr, *fd = nullptr, *rd = nullptr,
+           *J2d = nullptr, *T2d = nullptr, *cTd = nullptr;
+    int* hud = nullptr;
+    stage_lbmpc_model(st, d, D, &Dd);
+    st.in(&Dd.data, D->data, span(batch, D->sdata, (size_t)(d->mask ? 8 : 7) * d->q));
+    st.in(&Dd.x0, D->x0, span(batch, D->sx0, nx));
+    st.in(&Dd.Ain, D->Ain, m * n);
+    st.in(&Dd.bin, D->bin, span(batch, D->sbin, m));
+    st.in(&zd, z, B * n);
+    st.in(&dd, dstep, B * n);
+    // only what the call writes is staged: an output it leaves alone stays the caller's
+    if (cost) st.out(&cd, B, cost);
+    if (Jr) st.out(&Jd, B * nr * n, Jr);
+    if (er) st.out(&ed, B * nr, er);
+    if (H) st.out(&Hd, B * n * n, H);
+    if (f) st.out(&fd, B * n, f);
+    if (rhs && m) st.out(&rd, B * m, rhs);
+    if (hused) st.out(&hud, B, hused);
+    if (Jr2 && exact) st.out(&J2d, B * n2, Jr2);
+    if (Tr2 && exact) st.out(&T2d, B * n2, Tr2);
+    if (costT && dstep) st.out(&cTd, B * LB_NTRIAL, costT);
+    BQP_TRY(st.commit());
+    BQP_TRY(bqp_lbmpc_linearize_device(h, d, batch, &Dd, zd, dd, cd, Jd, ed, Hd, fd, rd, hud, J2d, T2d,
+                                       cTd, h->stream));
     return st.finish();
 }
 
