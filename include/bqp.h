@@ -537,6 +537,30 @@ typedef struct {
                        as 2 from the first iteration).  Honoured by bqp_nmpc_solve_batched[_device] and
                        bqp_closed_loop_nmpc[_device] in both loop modes; bqp_nmpc_linearize
                        ignores it.  Any other value is BQP_E_ARG */
+    int shooting;   /* 0 (a zero-initialised caller): single shooting - the states are eliminated,
+                       every SQP iterate is a rollout from the measured state.  1: direct multiple
+                       shooting, the form of the reference's NLP (y = [x_0..x_N; u; theta], the
+                       dynamics as equality rows): the states x_1..x_N stay decision variables (x_0
+                       is pinned to the measured state), the iterate is (X, z), and the stage
+                       sub-problem carries the defects c_k = dynamic(delta, x_k, u_k) - x_{k+1},
+                         dx_0 = 0,  dx_{k+1} = A_k dx_k + B_k du_k + c_k,
+                       with A_k, B_k, w_k, the bounds and hp formed at the iterate's own x_k - the
+                       structured solve's per-stage offset.  Merit function J + nu (V + E), V the
+                       rows' violation, E = sum_k |c_k|_1, nu <- max(nu, 1.1 max(max lam, max |pi|));
+                       the step test is over (dX, dz), feasibility is max(rows) <= 1e-9 and
+                       max |c_k| <= 1e-9, stationarity the full-space residual of bqp_ocp_duals'
+                       Lagrangian at the iterate against 10 tol (1 + |grad J|).  exitflag keeps its
+                       meaning; a non-finite dynamic() at an accepted iterate is -8.  No kernel of a
+                       round rolls out: the stages are linearised and the trial points evaluated
+                       in parallel; only a solve that is given no states rolls out z once, for its
+                       start.  Needs subproblem = 1; with subproblem = 0, with a weight in xs_lin /
+                       xs_quad that softens a row, or with rows that are no box rows it returns
+                       BQP_E_UNSUPPORTED.  Honoured by bqp_nmpc_solve_batched[_device] (which start
+                       from the rollout of z and return z alone), bqp_nmpc_dms_solve_batched[_device]
+                       and bqp_closed_loop_nmpc[_device] in both loop modes (warm start: z shifted,
+                       x_k <- x_{k+1}, x_N <- dynamic(delta, x_N, u_{N-1}) with the repeated move);
+                       bqp_nmpc_linearize, bqp_nmpc_stage_qp and bqp_nmpc_stage_cost do not read it.
+                       No MEX field.  Any other value is BQP_E_ARG */
 } bqp_nmpc_dims;
 
 typedef struct {
@@ -630,6 +654,32 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
                                   double* lam, double* cost, int* exitflag, int* iterations,
                                   void* stream);
 
+/* Multiple shooting (d->shooting must be 1, d->subproblem 1): the SQP solve with the states and the
+ * dynamics multipliers.  X (batch*(N+1)*4, absolute): in = the states of the start, out = those of
+ * the solution; X[:, 0] is overwritten with x0; X = NULL starts from the rollout of z (and returns
+ * no states) - bqp_nmpc_solve_batched's start.  pi (batch*N*4, may be NULL): the multipliers of
+ * x_{k+1} = dynamic(delta, x_k, u_k) in bqp_ocp_duals' sign convention; with lam, IPOPT's lam_g.
+ * Everything else as bqp_nmpc_solve_batched. */
+int bqp_nmpc_dms_solve_batched(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                               const bqp_nmpc_data* data, const bqp_options* opt, double* z, double* X,
+                               double* lam, double* pi, double* cost, int* exitflag, int* iterations);
+int bqp_nmpc_dms_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                                      const bqp_nmpc_data* data, const bqp_options* opt, double* z,
+                                      double* X, double* lam, double* pi, double* cost, int* exitflag,
+                                      int* iterations, void* stream);
+
+/* The multiple-shooting sub-problem at given states X (batch*(N+1)*4; stage 0 is taken from x0; NULL:
+ * the rollout of z) and z (batch*n) - the diagnostic counterpart of bqp_nmpc_stage_qp, whose
+ * outputs it has, and c (batch*N*4, may be NULL), the defects.  d->subproblem and d->shooting are
+ * not read. */
+int bqp_nmpc_dms_qp(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
+                    const double* X, const double* z, double* A, double* B, double* c, double* w,
+                    double* xlb, double* xub, double* ulb, double* uub, double* hp, double* W, double* Fp);
+int bqp_nmpc_dms_qp_device(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
+                           const double* X, const double* z, double* A, double* B, double* c, double* w,
+                           double* xlb, double* xub, double* ulb, double* uub, double* hp, double* W,
+                           double* Fp, void* stream);
+
 /* Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states: per step the
  * solve at the measured state, the RK4 plant with u_0 (cl->plant must be BQP_PLANT_MG_RK4,
  * cl->delta the plant's step; data->x0 is ignored), then the warm start - z shifted one stage
@@ -644,7 +694,7 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
  * and returns X = x_init.  X (batch*(steps+1)*4), U (batch*steps) absolute; exitflag and iterations
  * (batch*steps, may be NULL) per solve.  The loop's time goes to bqp_last_kernel_ms (6 launches
  * per round; on the stage route 6 and the structured solve's repair launch where opt->polish
- * asks for one), its rounds to bqp_last_loop_rounds.  The _device variant synchronises its stream
+ * asks for one; with shooting = 1 one more, the warm start of the states), its rounds to bqp_last_loop_rounds.  The _device variant synchronises its stream
  * while it polls for the instances that have finished. */
 int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
                          const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,

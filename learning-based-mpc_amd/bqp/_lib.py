@@ -77,8 +77,9 @@ class LbmpcData(C.Structure):
 
 
 class NmpcDims(C.Structure):
-    # subproblem: 0 dense route (the default of a four-argument construction), 1 stage route
-    _fields_ = [(n, C.c_int) for n in ('N', 'mx', 'mu', 'n_poly', 'subproblem')]
+    # subproblem: 0 dense route (the default of a four-argument construction), 1 stage route;
+    # shooting: 0 single shooting (the default of a five-argument construction), 1 multiple shooting
+    _fields_ = [(n, C.c_int) for n in ('N', 'mx', 'mu', 'n_poly', 'subproblem', 'shooting')]
 
 
 class NmpcData(C.Structure):
@@ -99,7 +100,9 @@ EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'b
            'bqp_nmpc_linearize', 'bqp_nmpc_linearize_device', 'bqp_nmpc_solve_batched',
            'bqp_nmpc_solve_batched_device', 'bqp_closed_loop_nmpc', 'bqp_closed_loop_nmpc_device',
            'bqp_last_loop_rounds', 'bqp_nmpc_stage_qp', 'bqp_nmpc_stage_qp_device',
-           'bqp_nmpc_stage_cost', 'bqp_lbmpc_linearize', 'bqp_lbmpc_linearize_device']
+           'bqp_nmpc_stage_cost', 'bqp_lbmpc_linearize', 'bqp_lbmpc_linearize_device',
+           'bqp_nmpc_dms_solve_batched', 'bqp_nmpc_dms_solve_batched_device', 'bqp_nmpc_dms_qp',
+           'bqp_nmpc_dms_qp_device']
 
 _lib = None
 
@@ -187,6 +190,13 @@ def load():
                                            C.POINTER(NmpcData), C.POINTER(Options), _PD, _PD, _PD,
                                            _PI, _PI]
     lib.bqp_nmpc_solve_batched_device.argtypes = lib.bqp_nmpc_solve_batched.argtypes + [C.c_void_p]
+    lib.bqp_nmpc_dms_solve_batched.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int,
+                                               C.POINTER(NmpcData), C.POINTER(Options)] + [_PD] * 5 + \
+        [_PI, _PI]
+    lib.bqp_nmpc_dms_solve_batched_device.argtypes = lib.bqp_nmpc_dms_solve_batched.argtypes + [C.c_void_p]
+    lib.bqp_nmpc_dms_qp.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int, C.POINTER(NmpcData)] + \
+        [_PD] * 13
+    lib.bqp_nmpc_dms_qp_device.argtypes = lib.bqp_nmpc_dms_qp.argtypes + [C.c_void_p]
     lib.bqp_closed_loop_nmpc.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int,
                                          C.POINTER(NmpcData), C.POINTER(Options), C.c_void_p, _PD,
                                          _PD, _PD, _PI, _PI]

@@ -9,6 +9,10 @@ the multipliers ``lam``, are in IPOPT's ``lam_g`` order with the dynamics rows r
 k = 1..N the rows of F_x then of F_u, then the terminal set.  ``functions/ocpNMPC.m`` (fmincon
 around an ode23 rollout) is not covered.
 
+With ``shooting='multiple'`` (stage route) the states are kept instead, as in the script: the
+iterate is ``(X, z)``, the solve returns ``X`` and the multipliers ``pi`` of the dynamics rows, and
+``lam`` with ``pi`` is ``lam_g`` (bqp_nmpc_dms_solve_batched, bqp_nmpc_dims.shooting in bqp.h).
+
 This module only marshals data; everything iterative runs on the GPU.
 """
 import ctypes as C
@@ -28,6 +32,15 @@ def _subproblem(name):
     if name not in _SUBPROBLEM:
         raise ValueError("subproblem is 'dense' or 'stage', not %r" % (name,))
     return _SUBPROBLEM[name]
+
+
+_SHOOTING = {'single': 0, 'multiple': 1}
+
+
+def _shooting(name):
+    if name not in _SHOOTING:
+        raise ValueError("shooting is 'single' or 'multiple', not %r" % (name,))
+    return _SHOOTING[name]
 
 
 def _f64(a):
@@ -60,8 +73,8 @@ class NMPC:
                       _f64(F_u.ravel()), _f64(np.asarray(h_u, float).ravel()),
                       _f64(F_T.T), _f64(np.asarray(h_w_N, float).ravel())]
 
-    def _dims(self, subproblem='dense'):
-        return _lib.NmpcDims(self.N, self.mx, self.mu, self.mp, _subproblem(subproblem))
+    def _dims(self, subproblem='dense', shooting='single'):
+        return _lib.NmpcDims(self.N, self.mx, self.mu, self.mp, _subproblem(subproblem), _shooting(shooting))
 
     def _data(self, x0=None, soft=(None, None)):
         return _lib.NmpcData(*[_lib.ptr(a) for a in self._keep], self.delta,
@@ -120,6 +133,32 @@ class NMPC:
         return OcpResult(A=np.swapaxes(Acm, 2, 3), B=B, w=w, xlb=xlb, xub=xub, ulb=ulb, uub=uub, hp=hp,
                          W=np.swapaxes(W, 1, 2), Fp=Fcm.T)
 
+    def dms_qp(self, xmeasure, X=None, z=None, handle=None):
+        """the multiple-shooting sub-problem at the iterate (X, z) (bqp_nmpc_dms_qp): X (batch,
+        N + 1, 4) absolute states (stage 0 is taken from xmeasure; None: the rollout of z).  Returns
+        stage_qp's blocks, formed at the iterate's own states, and c (batch, N, 4), the defects
+        dynamic(delta, x_k, u_k) - x_{k+1}."""
+        lib = _lib.load()
+        h = handle or _default_handle()
+        x0 = _f64(np.atleast_2d(xmeasure))
+        b, N, mp = x0.shape[0], self.N, self.mp
+        z = self._z(b, z)
+        if X is not None:
+            X = _f64(np.broadcast_to(np.asarray(X, float), (b, N + 1, 4))).copy()
+        Acm = np.zeros((b, N, 4, 4)); B = np.zeros((b, N, 4)); c = np.zeros((b, N, 4))
+        w = np.zeros((b, N + 1, 6))
+        xlb = np.zeros((b, N + 1, 4)); xub = np.zeros((b, N + 1, 4))
+        ulb = np.zeros((b, N)); uub = np.zeros((b, N)); hp = np.zeros((b, mp))
+        W = np.zeros((N + 1, 6, 6)); Fcm = np.zeros((6, mp))
+        dims, dd = self._dims('stage', 'multiple'), self._data(x0)
+        rc = lib.bqp_nmpc_dms_qp(h.value, C.byref(dims), b, C.byref(dd),
+                                 _lib.ptr(X) if X is not None else None, _lib.ptr(z), _lib.ptr(Acm),
+                                 _lib.ptr(B), _lib.ptr(c), _lib.ptr(w), _lib.ptr(xlb), _lib.ptr(xub),
+                                 _lib.ptr(ulb), _lib.ptr(uub), _lib.ptr(hp), _lib.ptr(W), _lib.ptr(Fcm))
+        _lib.check(rc, 'bqp_nmpc_dms_qp')
+        return OcpResult(A=np.swapaxes(Acm, 2, 3), B=B, c=c, w=w, xlb=xlb, xub=xub, ulb=ulb, uub=uub,
+                         hp=hp, W=np.swapaxes(W, 1, 2), Fp=Fcm.T)
+
     def stage_cost(self, xmeasure, z=None, xs_lin=None, xs_quad=None, handle=None):
         """what the stage route's merit function starts from at z (bqp_nmpc_stage_cost): cost
         (batch,) = J + penalty and penalty (batch,), the penalty of the softened rows at z."""
@@ -137,7 +176,7 @@ class NMPC:
         return OcpResult(cost=cost, penalty=pen)
 
     def solve(self, xmeasure, y0=None, z0=None, handle=None, max_iter=100, tol=1e-8, polish=0,
-              subproblem='dense', xs_lin=None, xs_quad=None):
+              subproblem='dense', xs_lin=None, xs_quad=None, shooting='single', X0=None):
         """xmeasure (batch, 4) absolute states; y0 a start in the script's layout
         [x_0..x_N; u; theta] (its states are ignored: they follow from u) or z0 = [u - u_eq;
         theta]; cold start u = u_eq, theta = 0 otherwise.  subproblem: 'dense' (the condensed
@@ -150,7 +189,18 @@ class NMPC:
         (bqp_nmpc_data in bqp.h).  Returns y_OL
         (batch, 4 (N + 1) + N + 1) in the script's layout, u0, theta, z, lam (batch, m), cost (with
         weights: J + penalty), exitflag, iterations, slack (batch, N, mx) = max(c, 0) on the
-        softened rows and 0 elsewhere, penalty (batch,)."""
+        softened rows and 0 elsewhere, penalty (batch,).
+        shooting: 'single' (the states eliminated) or 'multiple' (bqp_nmpc_dims.shooting = 1, stage
+        route only, no soft rows: the states stay decision variables).  With 'multiple', X0 (batch,
+        N + 1, 4) is the start's states (stage 0 is taken from xmeasure; None: the rollout of the
+        start's z), and the result also holds X (batch, N + 1, 4), the solution's states, and pi
+        (batch, N, 4), the multipliers of the dynamics rows; y_OL is then [X; u; theta] itself."""
+        if shooting == 'multiple':
+            return self._solve_dms(xmeasure, y0, z0, handle, max_iter, tol, polish, subproblem, xs_lin,
+                                   xs_quad, X0)
+        if X0 is not None:
+            raise ValueError("X0 belongs to shooting='multiple'")
+        _shooting(shooting)
         lib = _lib.load()
         h = handle or _default_handle()
         x0 = _f64(np.atleast_2d(xmeasure))
@@ -183,14 +233,49 @@ class NMPC:
                  u0=z[:, :1] + self.u_eq[0], theta=z[:, N:])
         return r
 
+    def _solve_dms(self, xmeasure, y0, z0, handle, max_iter, tol, polish, subproblem, xs_lin, xs_quad, X0):
+        """NMPC.solve with shooting='multiple' (bqp_nmpc_dms_solve_batched)"""
+        lib = _lib.load()
+        h = handle or _default_handle()
+        x0 = _f64(np.atleast_2d(xmeasure))
+        b, N, m = x0.shape[0], self.N, self.m
+        if y0 is not None:
+            y0 = np.atleast_2d(np.asarray(y0, float))
+            z0 = np.concatenate([y0[:, 4 * (N + 1):4 * (N + 1) + N] - self.u_eq[0], y0[:, -1:]], axis=1)
+            if X0 is None:
+                X0 = y0[:, :4 * (N + 1)].reshape(-1, N + 1, 4)
+        z = self._z(b, z0)
+        soft = self._soft(xs_lin, xs_quad)
+        dims, dd = self._dims(subproblem, 'multiple'), self._data(x0, soft)
+        if X0 is None:
+            # the rollout of the start's z, as the library's linearisation computes it
+            X = np.zeros((b, N + 1, 4))
+            d1 = self._dims()
+            rc = lib.bqp_nmpc_linearize(h.value, C.byref(d1), b, C.byref(dd), _lib.ptr(z), _lib.ptr(X),
+                                        None, None, None, None, None)
+            _lib.check(rc, 'bqp_nmpc_linearize')
+        else:
+            X = _f64(np.broadcast_to(np.asarray(X0, float), (b, N + 1, 4))).copy()
+        lam = np.zeros((b, m)); pi = np.zeros((b, N, 4)); cost = np.zeros(b)
+        flag = np.zeros(b, np.int32); it = np.zeros(b, np.int32)
+        o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
+        rc = lib.bqp_nmpc_dms_solve_batched(h.value, C.byref(dims), b, C.byref(dd), C.byref(o), _lib.ptr(z),
+                                            _lib.ptr(X), _lib.ptr(lam), _lib.ptr(pi), _lib.ptr(cost),
+                                            _lib.iptr(flag), _lib.iptr(it))
+        _lib.check(rc, 'bqp_nmpc_dms_solve_batched')
+        return OcpResult(z=z, X=X, lam=lam, pi=pi, cost=cost, exitflag=flag, iterations=it,
+                         y_OL=np.concatenate([X.reshape(b, -1), z[:, :N] + self.u_eq[0], z[:, N:]], axis=1),
+                         u0=z[:, :1] + self.u_eq[0], theta=z[:, N:])
+
 
 def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, polish=0,
-                     subproblem='dense', xs_lin=None, xs_quad=None):
+                     subproblem='dense', xs_lin=None, xs_quad=None, shooting='single'):
     """Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states x_init
     (batch, 4), absolute: per step the solve at the measured state, the RK4 plant with u_0, and
     the warm start (z shifted one stage, last move repeated, theta kept).  Every instance advances
     at its own step (with BQP_NMPC_SYNC set in the environment: the whole batch step by step, same
-    results).  subproblem, xs_lin and xs_quad as in NMPC.solve.  Returns X (batch, steps + 1, 4), U (batch, steps), exitflag and iterations
+    results).  subproblem, xs_lin, xs_quad and shooting as in NMPC.solve (with 'multiple' the warm
+    start also carries the states: x_k <- x_{k+1}, x_N stepped with the repeated last move).  Returns X (batch, steps + 1, 4), U (batch, steps), exitflag and iterations
     (batch, steps), kernel_ms, launches and rounds, the SQP rounds the loop launched."""
     lib = _lib.load()
     h = handle or _default_handle()
@@ -199,7 +284,7 @@ def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, p
     X = np.zeros((b, steps + 1, 4)); U = np.zeros((b, steps))
     fl = np.zeros((b, steps), np.int32); it = np.zeros((b, steps), np.int32)
     soft = prob._soft(xs_lin, xs_quad)
-    dims, dd = prob._dims(subproblem), prob._data(soft=soft)
+    dims, dd = prob._dims(subproblem, shooting), prob._data(soft=soft)
     cl = ClosedLoop(_BQP_PLANT_MG_RK4, steps, prob.delta, _lib.ptr(prob.x_eq), _lib.ptr(prob.u_eq))
     o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
     rc = lib.bqp_closed_loop_nmpc(h.value, C.byref(dims), b, C.byref(dd), C.byref(o), C.byref(cl),

@@ -1521,7 +1521,10 @@ static int nmpc_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
         (d->n_poly > 0 && (!D->F_T || !D->h_T)) || (need_x0 && !D->x0))
         return BQP_E_ARG;
     if (d->subproblem != 0 && d->subproblem != 1) return BQP_E_ARG;
+    if (d->shooting != 0 && d->shooting != 1) return BQP_E_ARG;
     if (!bqp::nmpc_supported(d->N, d->mx, d->mu)) return BQP_E_UNSUPPORTED;
+    // multiple shooting lives on the stage route: its sub-problem is the stage QP with defects
+    if (d->shooting == 1 && d->subproblem != 1) return BQP_E_UNSUPPORTED;
     const int64_t m = (int64_t)d->N * (d->mx + d->mu) + d->n_poly;
     if (m < 1 || m > 8192) return BQP_E_UNSUPPORTED;
     // stage route: the terminal rows are the structured kernel's polytope block
@@ -1667,16 +1670,22 @@ struct NmpcStageRoute {
     bool soft;
     bqp::NmpcSoftArgs q;
     const bqp::NmpcSoftArgs* softp() const { return soft ? &q : nullptr; }
+    // multiple shooting (bqp_nmpc_dims.shooting = 1): the states of the iterate over the workspace's
+    // Xw (the callers put their own array there), c_k = the defects, pi requested from the solve
+    bool dms;
+    bqp::NmpcDmsArgs m;
 };
 
 // use_soft = false: the weights of D are not read (the diagnostic bqp_nmpc_stage_qp)
 static int nmpc_stage_setup(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
                             const bqp_options& o, hipStream_t st, NmpcStageRoute& R,
-                            const bqp::NmpcStageArgs* user = nullptr, bool use_soft = true) {
+                            const bqp::NmpcStageArgs* user = nullptr, bool use_soft = true,
+                            bool dms = false) {
     const int N = d->N, n = N + 1, mp = d->n_poly, m = N * (d->mx + d->mu) + mp;
     const size_t B = batch;
     const bool want_soft = use_soft && nmpc_soft(D);
-    const layout::NworkStage NL(batch, N, mp, m, LB_NTRIAL, sizeof(bqp::NmpcBoundMap), want_soft ? 1 : 0);
+    const layout::NworkStage NL(batch, N, mp, m, LB_NTRIAL, sizeof(bqp::NmpcBoundMap), want_soft ? 1 : 0,
+                                dms ? 1 : 0);
     if (getenv("BQP_LB_TRACE"))
         fprintf(stderr, "bqp nmpc stage route: workspace %zu bytes for %d instances\n", NL.bytes, batch);
     HIP_TRY(h->nwork.reserve(NL.bytes));
@@ -1753,6 +1762,7 @@ static int nmpc_stage_setup(bqp_handle h, const bqp_nmpc_dims* d, int batch, con
     HIP_TRY(hipMemcpyAsync(&hm, s.map, sizeof(hm), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (hm.notbox || hm.unsupported) return BQP_E_UNSUPPORTED;
+    if (dms && want_soft && hm.anysoft) return BQP_E_UNSUPPORTED;   // soft rows: single shooting only
     R.soft = want_soft && hm.anysoft;
     memset(&R.od, 0, sizeof(R.od));
     R.od.nx = 4; R.od.nu = 1; R.od.np = 1; R.od.N = N; R.od.n_poly = mp; R.od.poly_stage = N;
@@ -1770,6 +1780,19 @@ static int nmpc_stage_setup(bqp_handle h, const bqp_nmpc_dims* d, int batch, con
     oD.hp = mp > 0 ? s.hp : nullptr; oD.shp = mp;
     oD.x0 = x0z; oD.sx0 = 0;
     oD.skip = a.done;
+    R.dms = dms;
+    memset(&R.m, 0, sizeof(R.m));
+    if (dms) {
+        R.m.X = layout::at<double>(nw, NL.Xw);
+        R.m.c = layout::at<double>(nw, NL.cdef);
+        R.m.dX = R.xo;
+        R.du.pi = layout::at<double>(nw, NL.piw);
+        R.m.pi = R.du.pi;
+        R.m.sw = layout::at<double>(nw, NL.sw);
+        R.m.gn = layout::at<double>(nw, NL.gn);
+        R.m.pimax = layout::at<double>(nw, NL.pimax);
+        oD.c = R.m.c; oD.sc = 4 * (int64_t)N;
+    }
     if (R.soft) {
         // the structured solve's soft state bounds: the tables shared by the batch, the slacks back
         oD.xs_lin = R.q.xsl; oD.xs_quad = R.q.xsq; oD.sxs = 0;
@@ -1802,12 +1825,23 @@ static int nmpc_stage_round(bqp_handle h, const NmpcStageRoute& R, hipStream_t s
         return BQP_OK;
     };
     BQP_TRY(mark(0));
-    HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st, R.softp()));
+    if (R.dms) HIP_TRY(bqp::launch_nmpc_dms_linearize(R.a, R.s, R.m, st));
+    else HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st, R.softp()));
     BQP_TRY(mark(1));
     BQP_TRY(bqp_solve_ocp_batched_device(h, &R.od, R.a.batch, &R.oD, &R.qo, R.xo, R.uo, R.tho, R.fv, R.sflag,
                                          nullptr, &R.du, st));
     *launches += h->launches;
     BQP_TRY(mark(2));
+    if (R.dms) {
+        HIP_TRY(bqp::launch_nmpc_dms_backmap(R.a, R.s, R.m, st));
+        BQP_TRY(mark(3));
+        HIP_TRY(bqp::launch_nmpc_dms_trial(R.a, R.m, st));
+        BQP_TRY(mark(4));
+        HIP_TRY(bqp::launch_nmpc_dms_update(R.a, R.m, st));
+        BQP_TRY(mark(5));
+        *launches += 4;
+        return BQP_OK;
+    }
     HIP_TRY(bqp::launch_nmpc_stage_backmap(R.a, R.s, st, R.softp()));
     BQP_TRY(mark(3));
     HIP_TRY(bqp::launch_nmpc_rollout(R.a, 0, st, R.softp()));
@@ -1818,23 +1852,32 @@ static int nmpc_stage_round(bqp_handle h, const NmpcStageRoute& R, hipStream_t s
     return BQP_OK;
 }
 
-// the stage route's form of bqp_nmpc_solve_batched_device (arguments checked there)
+// the stage route's form of bqp_nmpc_solve_batched_device (arguments checked there).  Multiple
+// shooting (d->shooting = 1): X (may be null: the workspace's) holds the states of the iterate, the
+// start where roll = false, else the rollout of z is the start; pi (may be null) takes the dynamics
+// multipliers
 static int nmpc_solve_stage(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
                             const bqp_options& o, double* z, double* lam, double* cost, int* exitflag,
-                            int* iterations, hipStream_t st) {
+                            int* iterations, hipStream_t st, double* X = nullptr, bool roll = true,
+                            double* pi = nullptr) {
     const size_t B = batch;
     NmpcStageRoute R;
-    BQP_TRY(nmpc_stage_setup(h, d, batch, D, o, st, R));
+    BQP_TRY(nmpc_stage_setup(h, d, batch, D, o, st, R, nullptr, true, d->shooting == 1));
     bqp::NmpcArgs& a = R.a;
     a.z = z; a.flag = exitflag; a.iters = iterations;
     if (lam) a.lam = lam;
+    if (R.dms) {
+        if (X) R.m.X = X;
+        if (pi) { R.du.pi = pi; R.m.pi = pi; }
+        if (roll || !X) HIP_TRY(bqp::launch_nmpc_dms_start(a, R.m, st));
+    }
     HIP_TRY(hipMemsetAsync(a.iters, 0, sizeof(int) * B, st));
     HIP_TRY(hipMemsetAsync(a.flag, 0, sizeof(int) * B, st));
     // the structured call records h->ev0 / ev1 for itself: this solve's start is an event of its own
     EventGuard e0;
     HIP_TRY(hipEventCreate(&e0.e));
     HIP_TRY(hipEventRecord(e0.e, st));
-    int launches = 1;                    // the table launch
+    int launches = 1 + ((R.dms && (roll || !X)) ? 1 : 0);   // the table launch, the start's rollout
     h->nmpc_rounds = 0;
     // BQP_LB_TRACE as on the dense route: 1 the sub-problems' exit flags, 2 per-launch event times
     const char* tenv = getenv("BQP_LB_TRACE");
@@ -2113,6 +2156,114 @@ int bqp_nmpc_solve_batched(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     return st.finish();
 }
 
+// multiple shooting (bqp_nmpc_dims.shooting = 1): the solve with the states and the dynamics
+// multipliers in its signature
+int bqp_nmpc_dms_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                                      const bqp_nmpc_data* D, const bqp_options* opt, double* z,
+                                      double* X, double* lam, double* pi, double* cost, int* exitflag,
+                                      int* iterations, void* stream) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z || !exitflag || !iterations || d->shooting != 1) return BQP_E_ARG;
+    BQP_TRY(nmpc_soft_check(d, D));
+    DevScope ds(h->device);
+    bqp_options o;
+    resolve(opt, &o);
+    return nmpc_solve_stage(h, d, batch, D, o, z, lam, cost, exitflag, iterations, (hipStream_t)stream, X,
+                            X == nullptr, pi);
+}
+
+int bqp_nmpc_dms_solve_batched(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                               const bqp_nmpc_data* D, const bqp_options* opt, double* z, double* X,
+                               double* lam, double* pi, double* cost, int* exitflag, int* iterations) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z || !exitflag || !iterations || d->shooting != 1) return BQP_E_ARG;
+    BQP_TRY(nmpc_soft_host_check(d, D));
+    BQP_TRY(nmpc_soft_check(d, D));
+    DevScope ds(h->device);
+    const size_t B = batch, N = d->N, n = N + 1, m = N * (size_t)(d->mx + d->mu) + d->n_poly;
+    Stage st(h);
+    bqp_nmpc_data Dd;
+    double *zd, *Xd = nullptr, *ld, *pd, *cd;
+    int *ed, *itd;
+    stage_nmpc_data(st, d, D, &Dd);
+    st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
+    st.in(&zd, z, B * n, z);   // the initial iterate, and the solution
+    st.in(&Xd, X, B * n * 4, X);
+    st.out(&ld, B * m, lam);
+    st.out(&pd, B * N * 4, pi);
+    st.out(&cd, B, cost);
+    st.out(&ed, B, exitflag);
+    st.out(&itd, B, iterations);
+    BQP_TRY(st.commit());
+    BQP_TRY(bqp_nmpc_dms_solve_batched_device(h, d, batch, &Dd, opt, zd, Xd, ld, pd, cd, ed, itd, h->stream));
+    return st.finish();
+}
+
+// the sub-problem at a given (X, z): the diagnostic counterpart of bqp_nmpc_stage_qp
+int bqp_nmpc_dms_qp_device(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                           const double* X, const double* z, double* A, double* B, double* c, double* w,
+                           double* xlb, double* xub, double* ulb, double* uub, double* hp, double* W,
+                           double* Fp, void* stream) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z) return BQP_E_ARG;
+    if (bqp::ocp_rpl_for(std::max(d->n_poly, 1)) < 0) return BQP_E_UNSUPPORTED;
+    DevScope ds(h->device);
+    hipStream_t st = (hipStream_t)stream;
+    bqp_options o;
+    resolve(nullptr, &o);
+    bqp::NmpcStageArgs user;
+    memset(&user, 0, sizeof(user));
+    user.A = A; user.B = B; user.w = w; user.xlb = xlb; user.xub = xub; user.ulb = ulb; user.uub = uub;
+    user.hp = hp; user.W = W; user.Fp = Fp;
+    NmpcStageRoute R;
+    BQP_TRY(nmpc_stage_setup(h, d, batch, D, o, st, R, &user, false, true));
+    R.a.z = const_cast<double*>(z);     // read only
+    if (c) R.m.c = c;
+    // the states into the workspace's copy (the linearisation pins its stage 0 to the measured state)
+    if (X) HIP_TRY(hipMemcpyAsync(R.m.X, X, sizeof(double) * batch * 4 * (size_t)(d->N + 1), hipMemcpyDeviceToDevice, st));
+    else HIP_TRY(bqp::launch_nmpc_dms_start(R.a, R.m, st));
+    HIP_TRY(bqp::launch_nmpc_dms_linearize(R.a, R.s, R.m, st));
+    return BQP_OK;
+}
+
+int bqp_nmpc_dms_qp(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                    const double* X, const double* z, double* A, double* B, double* c, double* w,
+                    double* xlb, double* xub, double* ulb, double* uub, double* hp, double* W, double* Fp) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_check(d, batch, D, true));
+    if (!z) return BQP_E_ARG;
+    BQP_TRY(nmpc_soft_host_check(d, D));
+    DevScope ds(h->device);
+    const size_t Bt = batch, N = d->N, mp = d->n_poly;
+    Stage st(h);
+    bqp_nmpc_data Dd;
+    const double *zd, *Xd = nullptr;
+    double *Ad = nullptr, *Bd = nullptr, *cd = nullptr, *wd = nullptr, *xld = nullptr, *xud = nullptr,
+           *uld = nullptr, *uud = nullptr, *hpd = nullptr, *Wd = nullptr, *Fpd = nullptr;
+    stage_nmpc_data(st, d, D, &Dd);
+    st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
+    st.in(&zd, z, Bt * (N + 1));
+    st.in(&Xd, X, Bt * (N + 1) * 4);
+    if (A) st.out(&Ad, Bt * N * 16, A);
+    if (B) st.out(&Bd, Bt * N * 4, B);
+    if (c) st.out(&cd, Bt * N * 4, c);
+    if (w) st.out(&wd, Bt * (N + 1) * 6, w);
+    if (xlb) st.out(&xld, Bt * (N + 1) * 4, xlb);
+    if (xub) st.out(&xud, Bt * (N + 1) * 4, xub);
+    if (ulb) st.out(&uld, Bt * N, ulb);
+    if (uub) st.out(&uud, Bt * N, uub);
+    if (hp && mp) st.out(&hpd, Bt * mp, hp);
+    if (W) st.out(&Wd, (N + 1) * 36, W);
+    if (Fp && mp) st.out(&Fpd, mp * 6, Fp);
+    BQP_TRY(st.commit());
+    BQP_TRY(bqp_nmpc_dms_qp_device(h, d, batch, &Dd, Xd, zd, Ad, Bd, cd, wd, xld, xud, uld, uud, hpd, Wd, Fpd,
+                                   h->stream));
+    return st.finish();
+}
+
 static int nmpc_loop_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
                            const bqp_closed_loop* cl, const double* x_init, const double* X,
                            const double* U) {
@@ -2137,12 +2288,14 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     // BQP_NMPC_SYNC selects the step-synchronous loop below (the asynchronous loop's bitwise
     // reference in tests/test_gpu_nmpc_async.py, and the path BQP_LB_TRACE reports on)
     const bool sync_loop = getenv("BQP_NMPC_SYNC") != nullptr;
-    const layout::CworkNmpc CL(batch, n, !sync_loop);
+    const bool dms = d->shooting == 1;
+    const layout::CworkNmpc CL(batch, n, !sync_loop, dms);
     HIP_TRY(h->cwork.reserve(CL.bytes));
     double* s = layout::at<double>(h->cwork.p, CL.s);
     double* z = layout::at<double>(h->cwork.p, CL.z);
     int* fl = layout::at<int>(h->cwork.p, CL.flags);
     int* it = layout::at<int>(h->cwork.p, CL.iters);
+    double* Xit = dms ? layout::at<double>(h->cwork.p, CL.Xit) : nullptr;   // the iterate's states
     HIP_TRY(bqp::launch_closed_loop_init(batch, 4, S, x_init, cl->x_eq, s, X, st));
     HIP_TRY(hipMemsetAsync(z, 0, sizeof(double) * B * n, st));   // cold start: u = u_eq, theta = 0
     EventGuard e0;
@@ -2172,7 +2325,7 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
         bqp::LbmpcArgs ne;
         bqp::DenseKernelArgs q;
         if (stage) {
-            BQP_TRY(nmpc_stage_setup(h, d, batch, &Dl, o, st, R));
+            BQP_TRY(nmpc_stage_setup(h, d, batch, &Dl, o, st, R, nullptr, true, dms));
             launches += 1;               // the table launch
         } else {
             HIP_TRY(nmpc_setup(h, d, batch, &Dl, o, nullptr, nullptr, nullptr, st, ad, ne, &q));
@@ -2181,6 +2334,13 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
         a.z = z; ne.z = z; a.flag = fl; a.iters = it;
         HIP_TRY(hipMemsetAsync(it, 0, sizeof(int) * B, st));
         HIP_TRY(hipMemsetAsync(fl, 0, sizeof(int) * B, st));
+        if (dms) {
+            // multiple shooting: the first solve starts from the rollout of the cold z, every later
+            // one from the warm start of the states
+            R.m.X = Xit;
+            HIP_TRY(bqp::launch_nmpc_dms_start(a, R.m, st));
+            launches += 1;
+        }
         // sub-problem polish only where the caller asks for it (bqp_nmpc_solve_batched_device), per
         // instance from its own SQP iteration count: mode 2 from LB_POLISH_STALL on
         q.polish = o.polish > 0 ? sub_polish(o.polish, false) : 0;
@@ -2206,6 +2366,10 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
                 HIP_TRY(bqp::launch_nmpc_update(a, st));
                 launches += 5;
             }
+            if (dms) {
+                HIP_TRY(bqp::launch_nmpc_dms_loop_states(batch, N, S, D->delta, D->u_eq, z, Xit, a.done, ts, st));
+                launches += 1;
+            }
             HIP_TRY(bqp::launch_nmpc_loop_advance(v, st));
             launches += 1;
             ++rounds;
@@ -2218,12 +2382,22 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     for (int t = 0; t < (sync_loop ? S : 0); ++t) {
         Dl.x0 = X + (int64_t)t * 4;      // the measured states X[:, t], absolute
         Dl.sx0 = (int64_t)(S + 1) * 4;
-        BQP_TRY(bqp_nmpc_solve_batched_device(h, d, batch, &Dl, opt, z, nullptr, nullptr, fl, it, stream));
+        if (dms) {
+            bqp_options o;
+            resolve(opt, &o);
+            BQP_TRY(nmpc_solve_stage(h, d, batch, &Dl, o, z, nullptr, nullptr, fl, it, st, Xit, t == 0));
+        } else {
+            BQP_TRY(bqp_nmpc_solve_batched_device(h, d, batch, &Dl, opt, z, nullptr, nullptr, fl, it, stream));
+        }
         launches += h->launches;
         rounds += h->nmpc_rounds;
         // the plant reads u_0 - u_eq = z[b, 0] (stride n)
         HIP_TRY(bqp::launch_mg_plant(cl->plant, batch, n, S, t, cl->delta, z, fl, cl->x_eq, cl->u_eq,
                                      s, X, U, exitflag, st));
+        if (dms) {
+            HIP_TRY(bqp::launch_nmpc_dms_loop_states(batch, N, S, D->delta, D->u_eq, z, Xit, nullptr, nullptr, st));
+            launches += 1;
+        }
         HIP_TRY(bqp::launch_nmpc_loop_shift(batch, N, S, t, z, it, iterations, st));
         launches += 2;
     }

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "bqp_nmpc_advance.h"
+#include "bqp_nmpc_dms.h"
 #include "bqp_nmpc_stage.h"
 #include "bqp_track.h"
 
@@ -213,7 +214,37 @@ struct NmpcSoftArgs {
     const double* sx;                 // batch x 8 (N+1): the structured solve's s_x
     double *pen0, *plin;              // batch each: the penalty at z, the sub-problem's model penalty
 };
+// Multiple shooting on the stage route (bqp_nmpc_dims.shooting = 1): the states of the iterate, the
+// defects and what the back-map hands to the update.  A separate, trailing kernel argument of the
+// nmpc_dms_* kernels; the indices are bqp_nmpc_dms.h's.
+static_assert(NMD_MAXN == NMPC_MAXN, "bqp_nmpc_dms.h's horizon limit");
+struct NmpcDmsArgs {
+    double* X;                 // batch x 4 (N+1): the iterate's states, absolute (in: start, out: solution)
+    double* c;                 // batch x 4 N: the defects c_k = f_k - x_{k+1}
+    const double* dX;          // batch x 4 (N+1): the structured solve's x
+    const double* pi;          // batch x 4 N: the structured solve's pi
+    double *sw, *gn, *pimax;   // batch each: sum w_k'v_k, |grad J|, max |pi|
+};
 bool nmpc_supported(int N, int mx, int mu);
+// multiple shooting: X = the rollout of z, for a solve that is given no states (once per solve)
+hipError_t launch_nmpc_dms_start(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st);
+// the linearisation at (X, z), lanes over the stages: A, B, c, w, bounds, hp, rhs, cost0
+hipError_t launch_nmpc_dms_linearize(const NmpcArgs& a, const NmpcStageArgs& s, const NmpcDmsArgs& m,
+                                     hipStream_t st);
+// after the structured solve: d, lam in NMPC row order, qpflag, sum w_k'v_k, the full-space
+// stationarity residual (a.stat), |grad J|, max |pi|
+hipError_t launch_nmpc_dms_backmap(const NmpcArgs& a, const NmpcStageArgs& s, const NmpcDmsArgs& m,
+                                   hipStream_t st);
+// the ntrial trial points (X, z) + 2^-t (dX, d): costT = J, violT = V + E
+hipError_t launch_nmpc_dms_trial(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st);
+hipError_t launch_nmpc_dms_update(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st);
+// closed loop, after a step's solve and before the warm start of z: the warm start of the states,
+// x_k <- x_{k+1}, x_N <- dynamic(delta, x_N, u_{N-1}) with the repeated last move (x_0 is the next
+// linearisation's, from the measured state).  done / ts null: every instance (step-synchronous
+// loop); else the instances nmpc_loop_advance_kernel is about to move to their next step
+hipError_t launch_nmpc_dms_loop_states(int batch, int N, int steps, double delta, const double* ueq,
+                                       const double* z, double* X, const int* done, const int* ts,
+                                       hipStream_t st);
 // stage route: the shared tables (W, Fp, bound map; with q also the weight tables), once per solve
 hipError_t launch_nmpc_stage_table(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
                                    const NmpcSoftArgs* q = nullptr);

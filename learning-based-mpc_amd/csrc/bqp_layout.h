@@ -143,9 +143,11 @@ struct NworkStage : Arena {
     Region A, B, w, xlb, xub, ulb, uub, hp, xo, uo, tho, fv, lamx, lamu, lamp;
     Region rhs, lam, d, f, ctl, cost0, costT, violT, stat, cprev, nu;
     Region xsl, xsq, sx, pen0, plin;   // soft state rows (soft = 1); empty otherwise
+    Region Xw, cdef, piw, sw, gn, pimax;   // multiple shooting (dms = 1); empty otherwise
     Region W, Fp, x0z, map;
     Region sflag, qpflag, done, ndone;
-    NworkStage(size_t Bt, size_t N, size_t mp, size_t m, size_t ntrial, size_t map_bytes, size_t soft = 0)
+    NworkStage(size_t Bt, size_t N, size_t mp, size_t m, size_t ntrial, size_t map_bytes, size_t soft = 0,
+               size_t dms = 0)
         : n(N + 1) {
         A = take<double>(Bt * N * 16);
         B = take<double>(Bt * N * 4);
@@ -180,6 +182,14 @@ struct NworkStage : Arena {
         sx = take<double>(soft * Bt * (N + 1) * 8);
         pen0 = take<double>(soft * Bt);
         plin = take<double>(soft * Bt);
+        // the iterate's states where the caller keeps none, the defects c_k, the structured solve's
+        // pi, and the back-map's sum w_k'v_k, |grad J| and max |pi|
+        Xw = take<double>(dms * Bt * (N + 1) * 4);
+        cdef = take<double>(dms * Bt * N * 4);
+        piw = take<double>(dms * Bt * N * 4);
+        sw = take<double>(dms * Bt);
+        gn = take<double>(dms * Bt);
+        pimax = take<double>(dms * Bt);
         W = take<double>((N + 1) * 36);
         Fp = take<double>(mp * 6);
         x0z = take<double>(4);
@@ -253,10 +263,11 @@ struct CworkSqp : Arena {
 // iterate (n), exit flags and iteration counts of the step.  The asynchronous loop (own_step)
 // adds the instances' step counters, the count of finished instances - nfin follows ts directly:
 // one memset zeroes both - and the measured state in absolute coordinates (4 per instance, the
-// solve's x0); the step-synchronous loop's layout is unchanged by it
+// solve's x0); the step-synchronous loop's layout is unchanged by it.  Multiple shooting (dms) adds
+// the iterate's states (4 n per instance) after everything else
 struct CworkNmpc : Arena {
-    Region s, z, flags, iters, ts, nfin, x0;
-    CworkNmpc(size_t B, size_t n, bool own_step = false) {
+    Region s, z, flags, iters, ts, nfin, x0, Xit;
+    CworkNmpc(size_t B, size_t n, bool own_step = false, bool dms = false) {
         s = take<double>(B * 4);
         z = take<double>(B * n);
         flags = take<int>(B);
@@ -266,6 +277,7 @@ struct CworkNmpc : Arena {
             nfin = take<int>(1);
             x0 = take<double>(B * 4);
         }
+        if (dms) Xit = take<double>(B * n * 4);
     }
 };
 

@@ -34,6 +34,9 @@
 //   nmpc_loop_shift_kernel      step-synchronous closed loop: the warm start of the next step
 //   nmpc_loop_advance_kernel    asynchronous closed loop, after every iteration: the instances
 //                               whose SQP has stopped move to their next closed-loop step
+// Multiple shooting on the stage route (bqp_nmpc_dims.shooting = 1; the nmpc_dms_* kernels below) =
+// dms linearise -> structured solve with the defects as its per-stage offset -> dms back-map ->
+// dms trials -> dms update: the states stay variables, lanes run over the stages, no rollout in a round
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -908,6 +911,506 @@ __global__ void __launch_bounds__(64) nmpc_stage_backmap_kernel(NmpcArgs a, Nmpc
 }
 
 // ------------------------------------------------------------------------------------------
+// multiple shooting on the stage route (bqp_nmpc_dims.shooting = 1): the states stay decision
+// variables.  The iterate is (X, z), X (N + 1) x 4 absolute with x_0 pinned to the measured state;
+// per stage k < N  f_k = dynamic(delta, x_k, u_k) (nm_rk4<true>, as the rollouts above), A_k, B_k its
+// Jacobians and the defect c_k = f_k - x_{k+1}; the sub-problem is the stage route's with
+//   dx_0 = 0,  dx_{k+1} = A_k dx_k + B_k du_k + c_k
+// and w_k, the bounds and hp from the iterate's own x_k (tests/nmpc_dms_ref.py).  Everything a
+// stage needs depends on (x_k, u_k, x_{k+1}, theta) alone, so a lane owns a stage: one wave per
+// instance, lanes over the stages in nmpc_dms_passes(N) <= 2 passes (bqp_nmpc_dms.h), the iterate
+// in LDS, wave sums for what is summed over the stages.  Only nmpc_dms_start_kernel, once per solve
+// that is given no states, rolls out.
+//   nmpc_dms_start_kernel      X = the rollout of z (a solve that starts without states)
+//   nmpc_dms_linearize_kernel  A_k | B_k | c_k | w_k, the rows as bounds, rhs = -rows, hp, cost0
+//   nmpc_dms_backmap_kernel    d, lam in NMPC row order, the sub-problem's flag, sum w_k'v_k, the
+//                              full-space stationarity residual, |grad J|, max |pi|
+//   nmpc_dms_trial_kernel      one wave per (instance, trial): J, V + E at (X, z) + 2^-t (dX, d)
+//   nmpc_dms_update_kernel     nu, Armijo, (X, z) += alpha (dX, d), the stopping clauses
+//   nmpc_dms_loop_states_kernel  closed loop: the warm start of the states
+// ------------------------------------------------------------------------------------------
+// weighted residual e = L (xx - x_eq - LAMBDA theta) as nmpc_stage_rollout_kernel's xgrad forms it:
+// J += e'e, wx = 2 L'e
+__device__ __forceinline__ void nmd_xgrad(const double* cst, int oL, const double (&xx)[4], double th,
+                                          double& J, double (&wx)[4]) {
+    double e[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        double er = 0.0;
+#pragma unroll
+        for (int c2 = r; c2 < 4; ++c2) er += cst[oL + 4 * r + c2] * (xx[c2] - cst[NO_XE + c2] - cst[NO_L + c2] * th);
+        J += er * er;
+        e[r] = er;
+    }
+#pragma unroll
+    for (int c2 = 0; c2 < 4; ++c2) {
+        double v = 0.0;
+#pragma unroll
+        for (int r = 0; r <= c2; ++r) v += cst[oL + 4 * r + c2] * e[r];
+        wx[c2] = 2.0 * v;
+    }
+}
+// theta entry of the stage gradient from its x and u entries: -LAMBDA'wx - PSI wu
+__device__ __forceinline__ double nmd_thgrad(const double* cst, const double (&wx)[4], double wu) {
+    double v = 0.0;
+#pragma unroll
+    for (int c2 = 0; c2 < 4; ++c2) v += cst[NO_L + c2] * wx[c2];
+    return -v - cst[NO_PSI] * wu;
+}
+// the terminal T term on LAMBDA theta: J += |Lt LAMBDA theta|^2, returns its theta gradient
+__device__ __forceinline__ double nmd_tterm(const double* cst, double th, double& J) {
+    double g = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        double w = 0.0;
+#pragma unroll
+        for (int c2 = r; c2 < 4; ++c2) w += cst[NO_T + 4 * r + c2] * cst[NO_L + c2];
+        const double e = w * th;
+        J += e * e;
+        g += 2.0 * w * e;
+    }
+    return g;
+}
+// value of row i of [F_x; F_u]: F_x (x - x_eq) - h_x (i < mx) or F_u v - h_u
+__device__ __forceinline__ double nmd_xrow(const double* cst, int mx, int i, const double (&x)[4]) {
+    double cv = -cst[NO_HX + i];
+#pragma unroll
+    for (int c2 = 0; c2 < 4; ++c2) cv += cst[NO_FX + i + mx * c2] * (x[c2] - cst[NO_XE + c2]);
+    return cv;
+}
+__device__ __forceinline__ double nmd_urow(const double* cst, int mx, int i, double v) {
+    return cst[NO_FU + i - mx] * v - cst[NO_HU + i - mx];
+}
+// the terminal rows F_T [x_N - x_eq; theta] - h_T, lanes over the rows: sum max(row, 0); STORE:
+// rhs = hp = -row
+template <bool STORE>
+__device__ __forceinline__ double nmd_term_rows(const NmpcArgs& a, const double* cst, int lane,
+                                                const double (&xN)[4], double th, double* rhsT, double* hp) {
+    const int mp = a.mp;
+    double Vt = 0.0;
+    for (int r = lane; r < mp; r += NM_WAVE) {
+        double F[5];
+#pragma unroll
+        for (int c2 = 0; c2 < 5; ++c2) F[c2] = a.FT[r + (int64_t)mp * c2];
+        double cv = F[4] * th - a.hT[r];
+#pragma unroll
+        for (int c2 = 0; c2 < 4; ++c2) cv += F[c2] * (xN[c2] - cst[NO_XE + c2]);
+        Vt += fmax(cv, 0.0);
+        if (STORE) { rhsT[r] = -cv; hp[r] = -cv; }
+    }
+    return Vt;
+}
+
+// a solve that is given no states starts from the rollout of z: the one serial chain of this route,
+// once per solve (every lane carries it, lane 0 stores); a solve given states does not launch it
+__global__ void __launch_bounds__(64) nmpc_dms_start_kernel(NmpcArgs a, NmpcDmsArgs m) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    if (b >= a.batch) return;
+    const int N = a.N;
+    const double* z = a.z + (int64_t)b * a.n;
+    double* X = m.X + (int64_t)b * nmpc_dms_x_stride(N);
+    const double ueq = a.ueq[0];
+    double x[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = a.x0[(int64_t)b * a.sx0 + i];
+    for (int k = 0; k <= N; ++k) {
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) X[nmpc_dms_x_index(k, i)] = x[i];
+        }
+        if (k == N) break;
+        double xn[4], AB[4][5];
+        nm_rk4<true>(a.delta, x, z[k] + ueq, xn, AB);   // <true>: the bits of the linearisation's f_k
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = xn[i];
+    }
+}
+
+// the iterate into LDS: zs = z + alpha d, Xs = X + alpha dX with stage 0 the measured state (the
+// caller syncs the wave); alpha = 0 reads neither d nor dX
+__device__ __forceinline__ void nmd_load_iterate(const NmpcArgs& a, const NmpcDmsArgs& m, int b, int lane,
+                                                 double alpha, double* zs, double* Xs) {
+    const int N = a.N, n = a.n;
+    const double* z = a.z + (int64_t)b * n;
+    const double* d = a.d + (int64_t)b * n;
+    const double* X = m.X + (int64_t)b * nmpc_dms_x_stride(N);
+    const double* dX = m.dX + (int64_t)b * nmpc_dms_x_stride(N);
+    for (int j = lane; j < n; j += NM_WAVE) zs[j] = alpha != 0.0 ? z[j] + alpha * d[j] : z[j];
+    for (int j = lane; j < 4 * (N + 1); j += NM_WAVE) {
+        double v;
+        if (j < 4) v = a.x0[(int64_t)b * a.sx0 + j];
+        else v = alpha != 0.0 ? X[j] + alpha * dX[j] : X[j];
+        Xs[j] = v;
+    }
+}
+
+__global__ void __launch_bounds__(64) nmpc_dms_linearize_kernel(NmpcArgs a, NmpcStageArgs s, NmpcDmsArgs m) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    if (b >= a.batch || a.done[b]) return;
+    const int N = a.N, mx = a.mx, mu = a.mu, ms = mx + mu, mp = a.mp;
+    __shared__ double zsh[NM_WAVE * NM_CPL];
+    __shared__ double Xs[NMD_XLDS];
+    __shared__ double cst[NO_END];
+    __shared__ NmpcBoundBox map;
+    nmd_load_iterate(a, m, b, lane, 0.0, zsh, Xs);
+    nm_load_consts(a, lane, cst);
+    nm_load_map(s.map, lane, &map);
+    wave_sync();
+    const double th = zsh[N], ueq = cst[NO_UE], psi = cst[NO_PSI];
+    double* Xg = m.X + (int64_t)b * nmpc_dms_x_stride(N);
+    double* cg = m.c + (int64_t)b * nmpc_dms_c_stride(N);
+    double* Ag = s.A + (int64_t)b * N * 16;
+    double* Bg = s.B + (int64_t)b * N * 4;
+    double* wg = s.w + (int64_t)b * (N + 1) * 6;
+    double* xlb = s.xlb + (int64_t)b * (N + 1) * 4;
+    double* xub = s.xub + (int64_t)b * (N + 1) * 4;
+    double* ulb = s.ulb + (int64_t)b * N;
+    double* uub = s.uub + (int64_t)b * N;
+    double* rhs = a.rhs + (int64_t)b * a.m;
+    if (lane < 4) Xg[lane] = Xs[lane];          // x_0 = the measured state, in the returned X too
+    // the bounds no row stands for (stage 0 of the state bounds is not read by the solve)
+    for (int i = lane; i < 4 * (N + 1); i += NM_WAVE) {
+        if (i < 4 || map.rowof[i & 3][0] < 0) xlb[i] = -INFINITY;
+        if (i < 4 || map.rowof[i & 3][1] < 0) xub[i] = INFINITY;
+    }
+    for (int i = lane; i < N; i += NM_WAVE) {
+        if (map.rowof[4][0] < 0) ulb[i] = -INFINITY;
+        if (map.rowof[4][1] < 0) uub[i] = INFINITY;
+    }
+    double J = 0.0;
+    const int np = nmpc_dms_passes(N);
+    for (int ps = 0; ps < np; ++ps) {
+        const int k = nmpc_dms_stage(N, lane, ps);
+        if (k < 0) continue;
+        double x[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = Xs[nmpc_dms_x_index(k, i)];
+        double wx[4], wu = 0.0, wt;
+        if (nmpc_dms_has_step(N, k)) {
+            const double vk = zsh[k];
+            nmd_xgrad(cst, NO_Q, x, th, J, wx);
+            const double lr = cst[NO_R];
+            const double eu = lr * (vk - psi * th);
+            J += eu * eu;
+            wu = 2.0 * lr * eu;
+            wt = nmd_thgrad(cst, wx, wu);
+            double xn[4], AB[4][5];
+            nm_rk4<true>(a.delta, x, vk + ueq, xn, AB);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int i = 0; i < 4; ++i) Ag[nmpc_dms_a_index(k, i, j)] = AB[i][j];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                Bg[nmpc_dms_b_index(k, i)] = AB[i][4];
+                cg[nmpc_dms_c_index(k, i)] = xn[i] - Xs[nmpc_dms_x_index(k + 1, i)];
+            }
+            // the rows of F_u on u_k: NMPC stage k + 1
+            for (int i = mx; i < ms; ++i) {
+                const double cv = nmd_urow(cst, mx, i, vk);
+                rhs[nmpc_stage_row(mx, mu, k + 1, i)] = -cv;
+                (map.side[i] ? uub : ulb)[nmpc_bound_index(map, mx, k + 1, i)] = nmpc_bound_value(map, i, -cv);
+            }
+        } else {
+            // terminal P on x_N, T on LAMBDA theta
+            nmd_xgrad(cst, NO_P, x, th, J, wx);
+            wt = nmd_thgrad(cst, wx, 0.0);
+            wt += nmd_tterm(cst, th, J);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) wg[nmpc_dms_w_index(k, i)] = wx[i];
+        wg[nmpc_dms_w_index(k, 4)] = wu;
+        wg[nmpc_dms_w_index(k, 5)] = wt;
+        // the rows of F_x on x_k: NMPC stage k
+        if (nmpc_dms_has_state_rows(N, k)) {
+            for (int i = 0; i < mx; ++i) {
+                const double cv = nmd_xrow(cst, mx, i, x);
+                rhs[nmpc_stage_row(mx, mu, k, i)] = -cv;
+                (map.side[i] ? xub : xlb)[nmpc_bound_index(map, mx, k, i)] = nmpc_bound_value(map, i, -cv);
+            }
+        }
+    }
+    double xN[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xN[i] = Xs[nmpc_dms_x_index(N, i)];
+    nmd_term_rows<true>(a, cst, lane, xN, th, rhs + nmpc_term_row(N, mx, mu, 0), s.hp + (int64_t)b * mp);
+    J = wsum(J);
+    if (lane == 0) a.cost0[b] = J;
+}
+
+// After the structured solve, one wave per instance (a finished instance leaves at once), lanes over
+// the stages.  The residual is that of the Lagrangian of bqp_ocp_duals (bqp.h) at the iterate:
+//   x_k (1 <= k <= N): w_k[x] + A_k'pi_k (k < N) - pi_{k-1} + F_x'lam_k (+ F_T[:, :4]'lam_T at N)
+//   u_k (k < N):       w_k[u] + B_k'pi_k + F_u'lam_{k+1}
+//   theta:             sum_k w_k[theta] + F_T[:, 4]'lam_T
+// and |grad J| the largest of the w entries it sums (theta: of the sum)
+__global__ void __launch_bounds__(64) nmpc_dms_backmap_kernel(NmpcArgs a, NmpcStageArgs s, NmpcDmsArgs m) {
+    const int lane = threadIdx.x, b = blockIdx.x;
+    if (b >= a.batch || a.done[b]) return;
+    const int N = a.N, n = a.n, mx = a.mx, mu = a.mu, mp = a.mp;
+    __shared__ NmpcBoundBox map;
+    nm_load_map(s.map, lane, &map);
+    wave_sync();
+    const double* uo = s.uo + (int64_t)b * N;
+    const double* lamx = s.lamx + (int64_t)b * (N + 1) * 8;
+    const double* lamu = s.lamu + (int64_t)b * N * 2;
+    const double* lamp = s.lamp + (int64_t)b * mp;
+    const double* dX = m.dX + (int64_t)b * nmpc_dms_x_stride(N);
+    const double* pi = m.pi + (int64_t)b * nmpc_dms_c_stride(N);
+    const double* A = s.A + (int64_t)b * N * 16;
+    const double* B = s.B + (int64_t)b * N * 4;
+    const double* w = s.w + (int64_t)b * (N + 1) * 6;
+    double* d = a.d + (int64_t)b * n;
+    double* lam = a.lam + (int64_t)b * a.m;
+    const double dth = s.tho[b];
+    for (int j = lane; j < N; j += NM_WAVE) d[j] = uo[j];
+    if (lane == 0) {
+        d[N] = dth;
+        a.qpflag[b] = s.sflag[b];
+    }
+    for (int r = lane; r < a.m; r += NM_WAVE) lam[r] = nmpc_stage_dual(map, N, mx, mu, r, lamx, lamu, lamp);
+    // F_T'lam_T: lanes over the rows, five wave sums
+    double tT[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int r = lane; r < mp; r += NM_WAVE) {
+        const double lr = lamp[r];
+#pragma unroll
+        for (int c2 = 0; c2 < 5; ++c2) tT[c2] = fma(a.FT[r + (int64_t)mp * c2], lr, tT[c2]);
+    }
+#pragma unroll
+    for (int c2 = 0; c2 < 5; ++c2) tT[c2] = wsum(tT[c2]);
+    // per (variable, side) the row's entry of F_x / F_u and its scale, as nmpc_stage_backmap_kernel
+    double Fe[NMS_NVAR][2], sc[NMS_NVAR][2];
+#pragma unroll
+    for (int v = 0; v < NMS_NVAR; ++v)
+#pragma unroll
+        for (int sd = 0; sd < 2; ++sd) {
+            const int i = map.rowof[v][sd];
+            Fe[v][sd] = i < 0 ? 0.0 : (v < 4 ? a.Fx[i + mx * v] : a.Fu[i - mx]);
+            sc[v][sd] = i < 0 ? 1.0 : map.scale[i];
+        }
+    double sw = 0.0, ths = 0.0, st = 0.0, gn = 0.0, pim = 0.0;
+    const int np = nmpc_dms_passes(N);
+    for (int ps = 0; ps < np; ++ps) {
+        const int k = nmpc_dms_stage(N, lane, ps);
+        if (k < 0) continue;
+        double wk[6], pk[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int e = 0; e < 6; ++e) wk[e] = w[nmpc_dms_w_index(k, e)];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sw += wk[i] * dX[nmpc_dms_x_index(k, i)];
+        sw += wk[5] * dth;
+        ths += wk[5];
+        if (nmpc_dms_has_step(N, k)) {
+            sw += wk[4] * uo[k];
+            double ru = wk[4] + Fe[4][0] * (lamu[nmpc_lamu_index(k, 0)] / sc[4][0]) +
+                        Fe[4][1] * (lamu[nmpc_lamu_index(k, 1)] / sc[4][1]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                pk[i] = pi[nmpc_dms_pi_index(k, i)];
+                pim = fmax(pim, fabs(pk[i]));
+                ru += B[nmpc_dms_b_index(k, i)] * pk[i];
+            }
+            st = fmax(st, fabs(ru));
+            gn = fmax(gn, fabs(wk[4]));
+        }
+        if (nmpc_dms_has_state_rows(N, k)) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                double r = wk[j] - pi[nmpc_dms_pi_index(k - 1, j)] +
+                           Fe[j][0] * (lamx[nmpc_lamx_index(k, 0, j)] / sc[j][0]) +
+                           Fe[j][1] * (lamx[nmpc_lamx_index(k, 1, j)] / sc[j][1]);
+                if (k == N) r += tT[j];
+                else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) r += A[nmpc_dms_a_index(k, i, j)] * pk[i];
+                }
+                st = fmax(st, fabs(r));
+                gn = fmax(gn, fabs(wk[j]));
+            }
+        }
+    }
+    sw = wsum(sw); ths = wsum(ths); st = wmax(st); gn = wmax(gn); pim = wmax(pim);
+    st = fmax(st, fabs(ths + tT[4]));
+    gn = fmax(gn, fabs(ths));
+    if (lane == 0) {
+        a.stat[b] = st;
+        m.sw[b] = sw;
+        m.gn[b] = gn;
+        m.pimax[b] = pim;
+    }
+}
+
+// one wave per (instance, trial): cost, row violation V and defect norm E = sum_k |f_k - x_{k+1}|_1
+// at (X, z) + 2^-t (dX, d), the stages in parallel; costT = J, violT = V + E (not finite where an f_k
+// is not: the update rejects the trial)
+__global__ void __launch_bounds__(64) nmpc_dms_trial_kernel(NmpcArgs a, NmpcDmsArgs m) {
+    const int lane = threadIdx.x;
+    const int nt = a.ntrial;
+    const int b = blockIdx.x / nt, t = blockIdx.x % nt;
+    if (b >= a.batch || a.done[b]) return;
+    const int N = a.N, mx = a.mx, ms = mx + a.mu;
+    __shared__ double zsh[NM_WAVE * NM_CPL];
+    __shared__ double Xs[NMD_XLDS];
+    __shared__ double cst[NO_END];
+    nmd_load_iterate(a, m, b, lane, ldexp(1.0, -t), zsh, Xs);
+    nm_load_consts(a, lane, cst);
+    wave_sync();
+    const double th = zsh[N], ueq = cst[NO_UE], psi = cst[NO_PSI];
+    double J = 0.0, V = 0.0, E = 0.0;
+    const int np = nmpc_dms_passes(N);
+    for (int ps = 0; ps < np; ++ps) {
+        const int k = nmpc_dms_stage(N, lane, ps);
+        if (k < 0) continue;
+        double x[4], wx[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) x[i] = Xs[nmpc_dms_x_index(k, i)];
+        if (nmpc_dms_has_step(N, k)) {
+            const double vk = zsh[k];
+            nmd_xgrad(cst, NO_Q, x, th, J, wx);
+            const double eu = cst[NO_R] * (vk - psi * th);
+            J += eu * eu;
+            double xn[4], AB[4][5];
+            nm_rk4<false>(a.delta, x, vk + ueq, xn, AB);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) E += fabs(xn[i] - Xs[nmpc_dms_x_index(k + 1, i)]);
+            for (int i = mx; i < ms; ++i) V += fmax(nmd_urow(cst, mx, i, vk), 0.0);
+        } else {
+            nmd_xgrad(cst, NO_P, x, th, J, wx);
+            nmd_tterm(cst, th, J);
+        }
+        if (nmpc_dms_has_state_rows(N, k))
+            for (int i = 0; i < mx; ++i) V += fmax(nmd_xrow(cst, mx, i, x), 0.0);
+    }
+    double xN[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) xN[i] = Xs[nmpc_dms_x_index(N, i)];
+    V += nmd_term_rows<false>(a, cst, lane, xN, th, nullptr, nullptr);
+    J = wsum(J); V = wsum(V); E = wsum(E);
+    if (lane == 0) {
+        a.costT[(int64_t)b * nt + t] = J;
+        a.violT[(int64_t)b * nt + t] = V + E;
+    }
+}
+
+// nmpc_update_kernel<true> for the iterate (X, z): the step over (dX, d), feasibility of the rows
+// and of the defects, the back-map's full-space stationarity against 10 tol (1 + |grad J|), the
+// merit function phi = J + nu (V + E) with nu <- max(nu, 1.1 max(max lam, max |pi|)) and
+// D = sum w_k'v_k - nu (V0 + E0)
+__global__ void __launch_bounds__(64) nmpc_dms_update_kernel(NmpcArgs a, NmpcDmsArgs m) {
+    const int b = blockIdx.x;
+    const int lane = threadIdx.x;
+    if (b >= a.batch || a.done[b]) return;
+    const int N = a.N, n = a.n, mr = a.m;
+    double* z = a.z + (int64_t)b * n;
+    const double* d = a.d + (int64_t)b * n;
+    double* X = m.X + (int64_t)b * nmpc_dms_x_stride(N);
+    const double* dX = m.dX + (int64_t)b * nmpc_dms_x_stride(N);
+    const double* c = m.c + (int64_t)b * nmpc_dms_c_stride(N);
+    const double* lam = a.lam + (int64_t)b * mr;
+    const double* rhs = a.rhs + (int64_t)b * mr;
+    const int qflag = a.qpflag[b];
+    double dn = 0.0, zn = 0.0, viol = -INFINITY, V0 = 0.0, lmax = 0.0, cmax = 0.0, E0 = 0.0;
+    for (int j = lane; j < n; j += NM_WAVE) {
+        dn = fmax(dn, fabs(d[j]));
+        zn = fmax(zn, fabs(z[j]));
+    }
+    for (int j = 4 + lane; j < 4 * (N + 1); j += NM_WAVE) dn = fmax(dn, fabs(dX[j]));
+    for (int r = lane; r < mr; r += NM_WAVE) {
+        const double cv = -rhs[r];
+        viol = fmax(viol, cv);
+        V0 += fmax(cv, 0.0);
+        lmax = fmax(lmax, lam[r]);
+    }
+    for (int j = lane; j < 4 * N; j += NM_WAVE) {
+        cmax = fmax(cmax, fabs(c[j]));
+        E0 += fabs(c[j]);
+    }
+    dn = wmax(dn); zn = wmax(zn); viol = wmax(viol); V0 = wsum(V0); lmax = wmax(lmax);
+    cmax = wmax(cmax); E0 = wsum(E0);
+    const double st = a.stat[b], gn = m.gn[b];
+    const bool feas0 = viol <= 1e-9 && cmax <= 1e-9;
+    const double VE0 = V0 + E0;
+    const double J0 = a.cost0[b];
+    int it = a.iters[b];
+    int flag = 0;
+    bool fin = false;
+    const bool qp_ok = qflag == 1 || ((qflag == 0 || qflag == -8) && isfinite(dn) && isfinite(st));
+    if (qflag == -2 || !qp_ok || !isfinite(J0) || !isfinite(VE0)) {
+        flag = (qflag == -2) ? -2 : -8;   // sub-problem infeasible / failed, or a non-finite iterate
+        fin = true;
+    } else if (feas0 && ((qflag == 1 && dn <= a.tol_step * (1.0 + zn) && st <= a.tol_stat * (1.0 + gn)) ||
+                         (it > 0 && dn <= 1e-6 * (1.0 + zn) &&
+                          (qflag != 1 || fabs(a.cprev[b] - J0) <= 1e-12 * (1.0 + fabs(J0)))))) {
+        flag = 1;
+        fin = true;
+    }
+    if (!fin) {
+        const double nu = fmax(a.nu[b], 1.1 * fmax(lmax, m.pimax[b]));
+        const double D = m.sw[b] - nu * VE0;
+        const double phi0 = J0 + nu * VE0;
+        int tsel = a.ntrial - 1;
+        for (int t = 0; t < a.ntrial; ++t) {
+            const double al = ldexp(1.0, -t);
+            const double Jt = a.costT[(int64_t)b * a.ntrial + t], Vt = a.violT[(int64_t)b * a.ntrial + t];
+            if (isfinite(Jt) && isfinite(Vt) && Jt + nu * Vt <= phi0 + 1e-4 * al * D) { tsel = t; break; }
+        }
+        const double Js = a.costT[(int64_t)b * a.ntrial + tsel];
+        if (!isfinite(Js) || !isfinite(a.violT[(int64_t)b * a.ntrial + tsel])) {
+            flag = -8;                    // the accepted iterate would not be finite
+            fin = true;
+        } else {
+            const double al = ldexp(1.0, -tsel);
+            for (int j = lane; j < n; j += NM_WAVE) z[j] += al * d[j];
+            for (int j = 4 + lane; j < 4 * (N + 1); j += NM_WAVE) X[j] += al * dX[j];
+            if (lane == 0) { a.cprev[b] = J0; a.nu[b] = nu; }
+            ++it;
+            if (it >= a.max_iter) {
+                flag = 0;
+                fin = true;
+                if (lane == 0) a.cost0[b] = Js;   // the returned iterate is the stepped one
+            }
+        }
+    }
+    if (lane == 0) {
+        a.iters[b] = it;
+        if (fin) {
+            a.flag[b] = flag;
+            a.done[b] = 1;
+            atomicAdd(a.ndone, 1);
+        }
+    }
+}
+
+// closed loop, after a step's solve and before the warm start of z (both loop modes launch this
+// kernel, so both step x_N with the same arithmetic): x_k <- x_{k+1} for k < N,
+// x_N <- dynamic(delta, x_N, u_{N-1}) with the move the shift of z repeats.  Stage 0 is the next
+// linearisation's, from the measured state.  done / ts null: every instance; else the instances
+// that nmpc_loop_advance_kernel moves to their next step in this round
+__global__ void __launch_bounds__(64) nmpc_dms_loop_states_kernel(int batch, int N, int steps, double delta,
+                                                                  const double* ueq, const double* z,
+                                                                  double* X, const int* done, const int* ts) {
+    __shared__ double Xs[NMD_XLDS];
+    const int b = blockIdx.x, lane = threadIdx.x;
+    if (b >= batch) return;
+    if (done && !(done[b] != 0 && ts[b] + 1 < steps)) return;   // uniform per wave
+    double* Xb = X + (int64_t)b * nmpc_dms_x_stride(N);
+    for (int j = lane; j < 4 * (N + 1); j += NM_WAVE) Xs[j] = Xb[j];
+    wave_sync();
+    for (int j = lane; j < 4 * N; j += NM_WAVE)
+        Xb[j] = Xs[nmpc_dms_x_index(nmpc_dms_shift_source(N, j >> 2), j & 3)];
+    double x[4], xn[4], AB[4][5];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = Xs[nmpc_dms_x_index(N, i)];
+    nm_rk4<true>(delta, x, z[(int64_t)b * (N + 1) + N - 1] + ueq[0], xn, AB);
+    if (lane < 4) {
+        double v = xn[0];
+#pragma unroll
+        for (int i = 1; i < 4; ++i) v = lane == i ? xn[i] : v;
+        Xb[nmpc_dms_x_index(N, lane)] = v;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // launch helpers
 // ------------------------------------------------------------------------------------------
 static bool nmpc_stage_args_ok(const NmpcArgs& a) {
@@ -946,6 +1449,60 @@ hipError_t launch_nmpc_stage_backmap(const NmpcArgs& a, const NmpcStageArgs& s, 
         return hipErrorInvalidValue;
     if (q) hipLaunchKernelGGL(nmpc_stage_backmap_kernel<true>, dim3(a.batch), dim3(64), 0, st, a, s, *q);
     else hipLaunchKernelGGL(nmpc_stage_backmap_kernel<false>, dim3(a.batch), dim3(64), 0, st, a, s, nm_hard);
+    return hipGetLastError();
+}
+
+static bool nmpc_dms_args_ok(const NmpcArgs& a, const NmpcDmsArgs& m) {
+    return nmpc_stage_args_ok(a) && 4 * (a.N + 1) <= NMD_XLDS && m.X && a.z && a.x0;
+}
+
+hipError_t launch_nmpc_dms_start(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st) {
+    if (!nmpc_dms_args_ok(a, m)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_dms_start_kernel, dim3(a.batch), dim3(64), 0, st, a, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_dms_linearize(const NmpcArgs& a, const NmpcStageArgs& s, const NmpcDmsArgs& m,
+                                     hipStream_t st) {
+    if (!nmpc_dms_args_ok(a, m) || !m.c || !s.A || !s.B || !s.w || !s.xlb || !s.xub || !s.ulb || !s.uub ||
+        (a.mp > 0 && !s.hp) || !s.map || !a.rhs || !a.cost0 || !a.done)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_dms_linearize_kernel, dim3(a.batch), dim3(64), 0, st, a, s, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_dms_backmap(const NmpcArgs& a, const NmpcStageArgs& s, const NmpcDmsArgs& m,
+                                   hipStream_t st) {
+    if (!nmpc_dms_args_ok(a, m) || !m.dX || !m.pi || !m.sw || !m.gn || !m.pimax || !s.A || !s.B || !s.w ||
+        !s.uo || !s.tho || !s.lamx || !s.lamu || (a.mp > 0 && !s.lamp) || !s.sflag || !s.map || !a.d ||
+        !a.lam || !a.stat || !a.qpflag)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_dms_backmap_kernel, dim3(a.batch), dim3(64), 0, st, a, s, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_dms_trial(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st) {
+    if (!nmpc_dms_args_ok(a, m) || !m.dX || !a.d || !a.costT || !a.violT || a.ntrial < 1)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_dms_trial_kernel, dim3(a.batch * a.ntrial), dim3(64), 0, st, a, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_dms_update(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st) {
+    if (!nmpc_dms_args_ok(a, m) || !m.dX || !m.c || !m.sw || !m.gn || !m.pimax || !a.d || !a.lam || !a.rhs ||
+        !a.costT || !a.violT || !a.stat || !a.cprev || !a.nu || !a.iters || !a.flag || !a.ndone)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_dms_update_kernel, dim3(a.batch), dim3(64), 0, st, a, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_dms_loop_states(int batch, int N, int steps, double delta, const double* ueq,
+                                       const double* z, double* X, const int* done, const int* ts,
+                                       hipStream_t st) {
+    if (batch < 1 || N < 1 || N > NMPC_MAXN || 4 * (N + 1) > NMD_XLDS || !ueq || !z || !X || (!done != !ts))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_dms_loop_states_kernel, dim3(batch), dim3(64), 0, st, batch, N, steps, delta, ueq,
+                       z, X, done, ts);
     return hipGetLastError();
 }
 

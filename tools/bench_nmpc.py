@@ -10,6 +10,8 @@ Warmed up; timed with the library's device events around work that ends in a syn
              default is the asynchronous loop); `loop_rounds` is printed in both modes
   --subproblem dense|stage   how the SQP's sub-problems are solved (default dense): condensed on
              the dense kernels, or in stage form on the structured kernel with per-stage models
+  --shooting single|multiple   bqp_nmpc_dims.shooting (default single; multiple needs --subproblem
+             stage): the states eliminated, or kept as decision variables
   --polish P the sub-problems' polish (bqp_options.polish; default 0)
   --split    also the split of an SQP iteration over linearise / normal equations / dense /
              trials / update (stage route: stage linearisation / structured solve / back-map /
@@ -54,9 +56,10 @@ def starts(batch, seed=11):
     return np.ascontiguousarray(x)
 
 
-def child(batch, subproblem, polish):
+def child(batch, subproblem, polish, shooting):
     import bqp
-    bqp.NMPC.solve(problem(), starts(batch), handle=bqp.Handle(0), subproblem=subproblem, polish=polish)
+    bqp.NMPC.solve(problem(), starts(batch), handle=bqp.Handle(0), subproblem=subproblem, polish=polish,
+                   shooting=shooting)
 
 
 def main():
@@ -68,6 +71,7 @@ def main():
     ap.add_argument('--split', action='store_true')
     ap.add_argument('--child', action='store_true')
     ap.add_argument('--subproblem', choices=('dense', 'stage'), default='dense')
+    ap.add_argument('--shooting', choices=('single', 'multiple'), default='single')
     ap.add_argument('--polish', type=int, default=0)
     ap.add_argument('--dump', default=None)
     ap.add_argument('--soft', type=float, nargs=2, metavar=('L1', 'L2'), default=None,
@@ -75,7 +79,7 @@ def main():
     a = ap.parse_args()
     soft = dict(xs_lin=a.soft[0], xs_quad=a.soft[1]) if a.soft else {}
     if a.child:
-        return child(a.batch, a.subproblem, a.polish)
+        return child(a.batch, a.subproblem, a.polish, a.shooting)
     import torch
     assert torch.cuda.is_available(), 'bench_nmpc.py needs a GPU'
     import bqp
@@ -83,20 +87,20 @@ def main():
     g = problem()
     x = starts(a.batch)
     for _ in range(a.warmup):
-        g.solve(x, handle=h, subproblem=a.subproblem, polish=a.polish)
+        g.solve(x, handle=h, subproblem=a.subproblem, polish=a.polish, shooting=a.shooting)
     lib = bqp.load()
     import ctypes as C
     from bqp import _lib
     # the solve alone (g.solve also rolls the solution out for y_OL): events around the SQP
     z = np.zeros((a.batch, N + 1)); lam = np.zeros((a.batch, g.m)); cost = np.zeros(a.batch)
     fl = np.zeros(a.batch, np.int32); it = np.zeros(a.batch, np.int32)
-    dims, dd = g._dims(a.subproblem), g._data(x)
+    dims, dd = g._dims(a.subproblem, a.shooting), g._data(x)
     o = _lib.options(max_iter=100, tol_stat=1e-8, polish=a.polish)
     _lib.check(lib.bqp_nmpc_solve_batched(h.value, C.byref(dims), a.batch, C.byref(dd), C.byref(o),
                                           _lib.ptr(z), _lib.ptr(lam), _lib.ptr(cost), _lib.iptr(fl),
                                           _lib.iptr(it)), 'bqp_nmpc_solve_batched')
     ms, launches = h.kernel_ms()
-    out = dict(N=N, batch=a.batch, m=g.m, subproblem=a.subproblem, polish=a.polish, solve_ms=ms, solves_per_s=a.batch / ms * 1e3,
+    out = dict(N=N, batch=a.batch, m=g.m, subproblem=a.subproblem, shooting=a.shooting, polish=a.polish, solve_ms=ms, solves_per_s=a.batch / ms * 1e3,
                solve_iterations_mean=float(it.mean()), solve_iterations_max=int(it.max()),
                solve_converged=float((fl == 1).mean()), solve_launches=launches,
                solve_flags={str(int(k)): int((fl == k).sum()) for k in np.unique(fl)})
@@ -114,8 +118,10 @@ def main():
             os.environ['BQP_NMPC_SYNC'] = '1'
         try:
             if a.warmup:
-                bqp.closed_loop_nmpc(g, xi, 2, handle=h, subproblem=a.subproblem, polish=a.polish, **soft)
-            r = bqp.closed_loop_nmpc(g, xi, a.steps, handle=h, subproblem=a.subproblem, polish=a.polish, **soft)
+                bqp.closed_loop_nmpc(g, xi, 2, handle=h, subproblem=a.subproblem, polish=a.polish,
+                                     shooting=a.shooting, **soft)
+            r = bqp.closed_loop_nmpc(g, xi, a.steps, handle=h, subproblem=a.subproblem, polish=a.polish,
+                                     shooting=a.shooting, **soft)
         finally:
             os.environ.pop('BQP_NMPC_SYNC', None)
         out.update(loop_soft=a.soft, loop_infeasible=int((r.exitflag == -2).sum()))
@@ -127,6 +133,8 @@ def main():
                    instance_steps_per_s=a.batch * a.steps / r.kernel_ms * 1e3,
                    loop_iterations_mean=float(r.iterations.mean()),
                    loop_iterations_max=int(r.iterations.max()),
+                   loop_iteration_histogram={str(int(k)): int((r.iterations == k).sum())
+                                             for k in np.unique(r.iterations)},
                    loop_at_iteration_limit=int((r.exitflag == 0).sum()),
                    loop_converged=float((r.exitflag == 1).mean()), loop_launches=r.launches)
         if a.dump:
@@ -134,7 +142,7 @@ def main():
     if a.split:
         env = dict(os.environ, BQP_LB_TRACE='2')
         c = subprocess.run([sys.executable, os.path.abspath(__file__), '--child', '--batch', str(a.batch),
-                            '--subproblem', a.subproblem, '--polish', str(a.polish)],
+                            '--subproblem', a.subproblem, '--polish', str(a.polish), '--shooting', a.shooting],
                            env=env, capture_output=True, text=True, timeout=600, check=True)
         if a.subproblem == 'dense':
             names = ('linearise', 'normal', 'dense', 'trials', 'update')
