@@ -501,7 +501,8 @@ int bqp_closed_loop_track_device(bqp_handle h, const bqp_ocp_dims* d, int batch,
  *   dynamics    x_{k+1} = dynamic(delta, x_k, u_k): one RK4 step of `system` (:217-223, :286-293),
  *               the plant BQP_PLANT_MG_RK4 steps; x_0 = the measured state (absolute)
  *   cost        sum_{k<N} [(x_k - x_eq - LAMBDA th)'(delta Q)(.) + (u_k - u_eq - PSI th)'(delta R)(.)]
- *               + (x_N - x_eq - LAMBDA th)'P(.) + (LAMBDA th)'T(LAMBDA th)
+ *               + (x_N - x_eq - LAMBDA th)'P(.) + (LAMBDA th - rho)'T(LAMBDA th - rho),
+ *               rho = x_ref - x_eq the set-point (bqp_nmpc_data.x_ref; 0 without one)
  *   rows c(z) <= 0, in this order: for k = 1..N  F_x (x_k - x_eq) - h_x (mx rows), then
  *               F_u (u_{k-1} - u_eq) - h_u (mu rows); then F_T [x_N - x_eq; theta] - h_T (n_poly
  *               rows).  m = N (mx + mu) + n_poly: IPOPT's lam_g order without the dynamics rows.
@@ -603,6 +604,29 @@ typedef struct {
      * modes, and bqp_nmpc_stage_cost; no MEX field. */
     const double* xs_lin;
     const double* xs_quad;
+    /* Set-point of the tracking cost (NULL, a zero-initialised caller: the working point x_eq, and
+     * every kernel runs as it did before these members existed).  x_ref holds 4 doubles per
+     * instance, the target state x_s in absolute coordinates; sx_ref is the distance in doubles
+     * between two instances' set-points, 0 = one set-point for the whole batch.  With
+     * rho = x_s - x_eq the offset term of the cost, (LAMBDA th)'T(LAMBDA th), becomes
+     *   (LAMBDA th - rho)'T(LAMBDA th - rho),
+     * in residual form the four rows (Lt LAMBDA) th - Lt rho; everything else - the running and
+     * terminal P cost, every row, the terminal set on [x_N - x_eq; theta] - is unchanged, and the
+     * set-point is constant over the horizon.  rho need not lie on the steady-state line LAMBDA th;
+     * a target the terminal set does not admit makes theta stop at that set's limit.  On the dense
+     * route only cost, the T rows of the residual and f[N] change, on the stage route and with
+     * multiple shooting only cost and the theta entry of w_N.  Honoured by bqp_nmpc_linearize,
+     * bqp_nmpc_stage_qp, bqp_nmpc_dms_qp, bqp_nmpc_stage_cost, bqp_nmpc_solve_batched,
+     * bqp_nmpc_dms_solve_batched (host and _device forms), on every route and with soft state
+     * rows, and by the closed loops (bqp_closed_loop_nmpc: a constant set-point;
+     * bqp_closed_loop_nmpc_track: a schedule).  On the dense route (subproblem = 0) a set-point
+     * also holds the sub-problems to 1e-2 opt->tol_stat and, with opt->polish = 0, polishes a
+     * sub-problem whose interior point ends 0 / -8 (opt->polish < 0 keeps the polish off): with
+     * theta on a terminal row the interior point otherwise reports convergence 5e-6 from the
+     * sub-problem's optimum.  A non-finite entry is BQP_E_ARG on the host entry
+     * points; on the _device entry points it is the caller's duty.  No MEX field. */
+    const double* x_ref;
+    int64_t sx_ref;
 } bqp_nmpc_data;
 
 /* Rollout and linearisation at given z (batch*n).  Outputs, each may be NULL: X (batch*(N+1)*4,
@@ -703,6 +727,39 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
                                 const bqp_nmpc_data* data, const bqp_options* opt,
                                 const bqp_closed_loop* cl, const double* x_init, double* X,
                                 double* U, int* exitflag, int* iterations, void* stream);
+
+/* Set-point schedule and disturbed plant of bqp_closed_loop_nmpc_track.  sref / sdist: the distance
+ * in doubles between two instances' schedules (>= steps*4), 0 = one schedule shared by the batch. */
+typedef struct {
+    const double* ref;   int64_t sref;   /* steps*4 per instance: the set-point x_s of every step,
+                                            absolute; NULL: data->x_ref at every step (NULL: x_eq) */
+    const double* dist;  int64_t sdist;  /* steps*4 per instance: added to the plant's state after
+                                            every step; NULL: 0 */
+    double* THETA;                       /* out, batch*steps, may be NULL: theta of every step's solution */
+} bqp_nmpc_track;
+
+/* bqp_closed_loop_nmpc with a set-point schedule and an additive state disturbance.  Step t of
+ * instance b: the solve at X[b,t] with the set-point ref[b,t] (bqp_nmpc_data.x_ref says how it enters
+ * the cost; constant over the horizon), U[b,t] = u_0, X[b,t+1] = dynamic(delta, X[b,t], U[b,t]) +
+ * dist[b,t] - one addition, rounded once, the value the log stores and the next solve measures - and
+ * THETA[b,t] = theta of that solution.  The warm start, the exit flags (a solve that ends != 1 still
+ * applies its u_0), the iteration counts, bqp_last_kernel_ms, bqp_last_loop_rounds and both loop
+ * modes (BQP_NMPC_SYNC) are bqp_closed_loop_nmpc's, on every route it has - dense, stage, stage
+ * with soft state rows, multiple shooting - with the same launches per round: the advance launch
+ * also logs theta, adds the disturbance and, while steps remain, takes the instance's next
+ * set-point (it never reads ref[b, steps]); both modes return the same bits.  tr = NULL is
+ * bqp_closed_loop_nmpc.  steps = 0 returns X = x_init.  A non-finite entry of ref or dist is
+ * BQP_E_ARG on the host entry point.  Not covered: a set-point that varies over the horizon, a
+ * plant whose parameters differ from the model's (the disturbance is additive), a MEX field. */
+int bqp_closed_loop_nmpc_track(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
+                               const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,
+                               const bqp_nmpc_track* tr, double* X, double* U, int* exitflag,
+                               int* iterations);
+int bqp_closed_loop_nmpc_track_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                                      const bqp_nmpc_data* data, const bqp_options* opt,
+                                      const bqp_closed_loop* cl, const double* x_init,
+                                      const bqp_nmpc_track* tr, double* X, double* U, int* exitflag,
+                                      int* iterations, void* stream);
 
 /* Timing of the most recent solve on this handle: kernel time measured with hipEvents on the
  * launch stream (ms), and the number of kernel launches it covered. */

@@ -86,7 +86,14 @@ class NmpcData(C.Structure):
     _fields_ = [(n, _PD) for n in ('Lq', 'Lr', 'Lp', 'Lt', 'LAMBDA', 'PSI', 'x_eq', 'u_eq', 'F_x',
                                    'h_x', 'F_u', 'h_u', 'F_T', 'h_T')] + \
                [('delta', C.c_double), ('x0', _PD), ('sx0', C.c_int64),
-                ('xs_lin', _PD), ('xs_quad', _PD)]     # soft state rows: mx weights each, or NULL
+                ('xs_lin', _PD), ('xs_quad', _PD),     # soft state rows: mx weights each, or NULL
+                ('x_ref', _PD), ('sx_ref', C.c_int64)]  # set-point: 4 per instance (stride 0: shared), or NULL
+
+
+class NmpcTrack(C.Structure):
+    # bqp_closed_loop_nmpc_track: set-point schedule, disturbance (steps*4 per instance, stride 0:
+    # shared; NULL: none) and the theta log (batch*steps, or NULL)
+    _fields_ = [('ref', _PD), ('sref', C.c_int64), ('dist', _PD), ('sdist', C.c_int64), ('THETA', _PD)]
 
 
 EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'bqp_build_source_sha1',
@@ -102,7 +109,7 @@ EXPORTS = ['bqp_create', 'bqp_destroy', 'bqp_default_options', 'bqp_version', 'b
            'bqp_last_loop_rounds', 'bqp_nmpc_stage_qp', 'bqp_nmpc_stage_qp_device',
            'bqp_nmpc_stage_cost', 'bqp_lbmpc_linearize', 'bqp_lbmpc_linearize_device',
            'bqp_nmpc_dms_solve_batched', 'bqp_nmpc_dms_solve_batched_device', 'bqp_nmpc_dms_qp',
-           'bqp_nmpc_dms_qp_device']
+           'bqp_nmpc_dms_qp_device', 'bqp_closed_loop_nmpc_track', 'bqp_closed_loop_nmpc_track_device']
 
 _lib = None
 
@@ -201,6 +208,10 @@ def load():
                                          C.POINTER(NmpcData), C.POINTER(Options), C.c_void_p, _PD,
                                          _PD, _PD, _PI, _PI]
     lib.bqp_closed_loop_nmpc_device.argtypes = lib.bqp_closed_loop_nmpc.argtypes + [C.c_void_p]
+    lib.bqp_closed_loop_nmpc_track.argtypes = [C.c_void_p, C.POINTER(NmpcDims), C.c_int,
+                                               C.POINTER(NmpcData), C.POINTER(Options), C.c_void_p, _PD,
+                                               C.POINTER(NmpcTrack), _PD, _PD, _PI, _PI]
+    lib.bqp_closed_loop_nmpc_track_device.argtypes = lib.bqp_closed_loop_nmpc_track.argtypes + [C.c_void_p]
     lib.bqp_last_loop_rounds.argtypes = [C.c_void_p, _PI]
     _lib = lib
     return lib

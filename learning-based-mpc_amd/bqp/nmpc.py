@@ -76,10 +76,24 @@ class NMPC:
     def _dims(self, subproblem='dense', shooting='single'):
         return _lib.NmpcDims(self.N, self.mx, self.mu, self.mp, _subproblem(subproblem), _shooting(shooting))
 
-    def _data(self, x0=None, soft=(None, None)):
+    def _data(self, x0=None, soft=(None, None), x_ref=None):
+        """x_ref: None or what _ref returns, (4,) for the batch or (batch, 4) (the caller keeps it
+        alive over the call)"""
         return _lib.NmpcData(*[_lib.ptr(a) for a in self._keep], self.delta,
                              _lib.ptr(x0) if x0 is not None else None, 4,
-                             *[_lib.ptr(a) if a is not None else None for a in soft])
+                             *[_lib.ptr(a) if a is not None else None for a in soft],
+                             _lib.ptr(x_ref) if x_ref is not None else None,
+                             0 if x_ref is None or x_ref.ndim == 1 else 4)
+
+    @staticmethod
+    def _ref(x_ref, b):
+        """the set-point as the C structure takes it: None, (4,) shared by the batch, or (b, 4)"""
+        if x_ref is None:
+            return None
+        r = _f64(np.asarray(x_ref, float))
+        if r.shape not in ((4,), (b, 4)):
+            raise ValueError('x_ref has the shape (4,) or (batch, 4) = (%d, 4), not %r' % (b, r.shape))
+        return r
 
     def _soft(self, xs_lin, xs_quad):
         """the row weights as the C structure takes them: None, or mx doubles (a scalar is every
@@ -92,10 +106,13 @@ class NMPC:
             return np.zeros((b, self.n))
         return _f64(np.broadcast_to(np.atleast_2d(np.asarray(z, float)), (b, self.n))).copy()
 
-    def linearize(self, xmeasure, z=None, handle=None):
+    def linearize(self, xmeasure, z=None, handle=None, x_ref=None):
         """rollout and linearisation at z (batch, N + 1) = [u - u_eq; theta] from the measured
         states xmeasure (batch, 4), absolute.  Returns X (batch, N + 1, 4), cost (batch,),
-        c (batch, m), C (batch, m, n) = dc/dz, H (batch, n, n) = 2 Jr'Jr, f (batch, n)."""
+        c (batch, m), C (batch, m, n) = dc/dz, H (batch, n, n) = 2 Jr'Jr, f (batch, n).
+        x_ref: the set-point of the tracking cost, absolute, (4,) for the whole batch or (batch, 4)
+        (bqp_nmpc_data.x_ref; None: the working point x_eq) - here and in stage_qp, dms_qp,
+        stage_cost and solve."""
         lib = _lib.load()
         h = handle or _default_handle()
         x0 = _f64(np.atleast_2d(xmeasure))
@@ -103,14 +120,15 @@ class NMPC:
         z = self._z(b, z)
         X = np.zeros((b, self.N + 1, 4)); cost = np.zeros(b); c = np.zeros((b, m))
         Ccm = np.zeros((b, n, m)); H = np.zeros((b, n, n)); f = np.zeros((b, n))
-        dims, dd = self._dims(), self._data(x0)
+        xr = self._ref(x_ref, b)
+        dims, dd = self._dims(), self._data(x0, x_ref=xr)
         rc = lib.bqp_nmpc_linearize(h.value, C.byref(dims), b, C.byref(dd), _lib.ptr(z), _lib.ptr(X),
                                     _lib.ptr(cost), _lib.ptr(c), _lib.ptr(Ccm), _lib.ptr(H),
                                     _lib.ptr(f))
         _lib.check(rc, 'bqp_nmpc_linearize')
         return OcpResult(X=X, cost=cost, c=c, C=np.swapaxes(Ccm, 1, 2), H=H, f=f)
 
-    def stage_qp(self, xmeasure, z=None, handle=None):
+    def stage_qp(self, xmeasure, z=None, handle=None, x_ref=None):
         """the stage sub-problem at z as the stage route hands it to the structured solve
         (bqp_nmpc_stage_qp), in v_k = [dx_k; du_k; dtheta]: A (batch, N, 4, 4), B (batch, N, 4),
         w (batch, N + 1, 6), xlb / xub (batch, N + 1, 4; stage 0 is -inf / +inf), ulb / uub
@@ -124,7 +142,8 @@ class NMPC:
         xlb = np.zeros((b, N + 1, 4)); xub = np.zeros((b, N + 1, 4))
         ulb = np.zeros((b, N)); uub = np.zeros((b, N)); hp = np.zeros((b, mp))
         W = np.zeros((N + 1, 6, 6)); Fcm = np.zeros((6, mp))
-        dims, dd = self._dims(), self._data(x0)
+        xr = self._ref(x_ref, b)
+        dims, dd = self._dims(), self._data(x0, x_ref=xr)
         rc = lib.bqp_nmpc_stage_qp(h.value, C.byref(dims), b, C.byref(dd), _lib.ptr(z), _lib.ptr(Acm),
                                    _lib.ptr(B), _lib.ptr(w), _lib.ptr(xlb), _lib.ptr(xub),
                                    _lib.ptr(ulb), _lib.ptr(uub), _lib.ptr(hp), _lib.ptr(W),
@@ -133,7 +152,7 @@ class NMPC:
         return OcpResult(A=np.swapaxes(Acm, 2, 3), B=B, w=w, xlb=xlb, xub=xub, ulb=ulb, uub=uub, hp=hp,
                          W=np.swapaxes(W, 1, 2), Fp=Fcm.T)
 
-    def dms_qp(self, xmeasure, X=None, z=None, handle=None):
+    def dms_qp(self, xmeasure, X=None, z=None, handle=None, x_ref=None):
         """the multiple-shooting sub-problem at the iterate (X, z) (bqp_nmpc_dms_qp): X (batch,
         N + 1, 4) absolute states (stage 0 is taken from xmeasure; None: the rollout of z).  Returns
         stage_qp's blocks, formed at the iterate's own states, and c (batch, N, 4), the defects
@@ -150,7 +169,8 @@ class NMPC:
         xlb = np.zeros((b, N + 1, 4)); xub = np.zeros((b, N + 1, 4))
         ulb = np.zeros((b, N)); uub = np.zeros((b, N)); hp = np.zeros((b, mp))
         W = np.zeros((N + 1, 6, 6)); Fcm = np.zeros((6, mp))
-        dims, dd = self._dims('stage', 'multiple'), self._data(x0)
+        xr = self._ref(x_ref, b)
+        dims, dd = self._dims('stage', 'multiple'), self._data(x0, x_ref=xr)
         rc = lib.bqp_nmpc_dms_qp(h.value, C.byref(dims), b, C.byref(dd),
                                  _lib.ptr(X) if X is not None else None, _lib.ptr(z), _lib.ptr(Acm),
                                  _lib.ptr(B), _lib.ptr(c), _lib.ptr(w), _lib.ptr(xlb), _lib.ptr(xub),
@@ -159,7 +179,7 @@ class NMPC:
         return OcpResult(A=np.swapaxes(Acm, 2, 3), B=B, c=c, w=w, xlb=xlb, xub=xub, ulb=ulb, uub=uub,
                          hp=hp, W=np.swapaxes(W, 1, 2), Fp=Fcm.T)
 
-    def stage_cost(self, xmeasure, z=None, xs_lin=None, xs_quad=None, handle=None):
+    def stage_cost(self, xmeasure, z=None, xs_lin=None, xs_quad=None, handle=None, x_ref=None):
         """what the stage route's merit function starts from at z (bqp_nmpc_stage_cost): cost
         (batch,) = J + penalty and penalty (batch,), the penalty of the softened rows at z."""
         lib = _lib.load()
@@ -169,14 +189,15 @@ class NMPC:
         z = self._z(b, z)
         cost = np.zeros(b); pen = np.zeros(b)
         soft = self._soft(xs_lin, xs_quad)
-        dims, dd = self._dims('stage'), self._data(x0, soft)
+        xr = self._ref(x_ref, b)
+        dims, dd = self._dims('stage'), self._data(x0, soft, xr)
         rc = lib.bqp_nmpc_stage_cost(h.value, C.byref(dims), b, C.byref(dd), _lib.ptr(z), _lib.ptr(cost),
                                      _lib.ptr(pen))
         _lib.check(rc, 'bqp_nmpc_stage_cost')
         return OcpResult(cost=cost, penalty=pen)
 
     def solve(self, xmeasure, y0=None, z0=None, handle=None, max_iter=100, tol=1e-8, polish=0,
-              subproblem='dense', xs_lin=None, xs_quad=None, shooting='single', X0=None):
+              subproblem='dense', xs_lin=None, xs_quad=None, shooting='single', X0=None, x_ref=None):
         """xmeasure (batch, 4) absolute states; y0 a start in the script's layout
         [x_0..x_N; u; theta] (its states are ignored: they follow from u) or z0 = [u - u_eq;
         theta]; cold start u = u_eq, theta = 0 otherwise.  subproblem: 'dense' (the condensed
@@ -194,10 +215,12 @@ class NMPC:
         route only, no soft rows: the states stay decision variables).  With 'multiple', X0 (batch,
         N + 1, 4) is the start's states (stage 0 is taken from xmeasure; None: the rollout of the
         start's z), and the result also holds X (batch, N + 1, 4), the solution's states, and pi
-        (batch, N, 4), the multipliers of the dynamics rows; y_OL is then [X; u; theta] itself."""
+        (batch, N, 4), the multipliers of the dynamics rows; y_OL is then [X; u; theta] itself.
+        x_ref: the set-point, as in linearize; theta then settles where LAMBDA theta is closest to
+        x_ref - x_eq in the T norm, within the terminal set."""
         if shooting == 'multiple':
             return self._solve_dms(xmeasure, y0, z0, handle, max_iter, tol, polish, subproblem, xs_lin,
-                                   xs_quad, X0)
+                                   xs_quad, X0, x_ref)
         if X0 is not None:
             raise ValueError("X0 belongs to shooting='multiple'")
         _shooting(shooting)
@@ -212,7 +235,8 @@ class NMPC:
         lam = np.zeros((b, m)); cost = np.zeros(b)
         flag = np.zeros(b, np.int32); it = np.zeros(b, np.int32)
         soft = self._soft(xs_lin, xs_quad)
-        dims, dd = self._dims(subproblem), self._data(x0, soft)
+        xr = self._ref(x_ref, b)
+        dims, dd = self._dims(subproblem), self._data(x0, soft, xr)
         o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
         rc = lib.bqp_nmpc_solve_batched(h.value, C.byref(dims), b, C.byref(dd), C.byref(o),
                                         _lib.ptr(z), _lib.ptr(lam), _lib.ptr(cost), _lib.iptr(flag),
@@ -233,7 +257,8 @@ class NMPC:
                  u0=z[:, :1] + self.u_eq[0], theta=z[:, N:])
         return r
 
-    def _solve_dms(self, xmeasure, y0, z0, handle, max_iter, tol, polish, subproblem, xs_lin, xs_quad, X0):
+    def _solve_dms(self, xmeasure, y0, z0, handle, max_iter, tol, polish, subproblem, xs_lin, xs_quad, X0,
+                   x_ref=None):
         """NMPC.solve with shooting='multiple' (bqp_nmpc_dms_solve_batched)"""
         lib = _lib.load()
         h = handle or _default_handle()
@@ -246,7 +271,8 @@ class NMPC:
                 X0 = y0[:, :4 * (N + 1)].reshape(-1, N + 1, 4)
         z = self._z(b, z0)
         soft = self._soft(xs_lin, xs_quad)
-        dims, dd = self._dims(subproblem, 'multiple'), self._data(x0, soft)
+        xr = self._ref(x_ref, b)
+        dims, dd = self._dims(subproblem, 'multiple'), self._data(x0, soft, xr)
         if X0 is None:
             # the rollout of the start's z, as the library's linearisation computes it
             X = np.zeros((b, N + 1, 4))
@@ -268,15 +294,36 @@ class NMPC:
                          u0=z[:, :1] + self.u_eq[0], theta=z[:, N:])
 
 
+def _schedule(a, b, steps, name):
+    """a schedule as bqp_nmpc_track takes it: (array, stride) from (steps, 4), shared by the batch, or
+    (batch, steps, 4)"""
+    if a is None:
+        return None, 0
+    a = _f64(np.asarray(a, float))
+    if a.shape == (steps, 4):
+        return a, 0
+    if a.shape == (b, steps, 4):
+        return a, steps * 4
+    raise ValueError('%s has the shape (steps, 4) or (batch, steps, 4) = (%d, %d, 4), not %r'
+                     % (name, b, steps, a.shape))
+
+
 def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, polish=0,
-                     subproblem='dense', xs_lin=None, xs_quad=None, shooting='single'):
+                     subproblem='dense', xs_lin=None, xs_quad=None, shooting='single', refs=None,
+                     dist=None, x_ref=None):
     """Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states x_init
     (batch, 4), absolute: per step the solve at the measured state, the RK4 plant with u_0, and
     the warm start (z shifted one stage, last move repeated, theta kept).  Every instance advances
     at its own step (with BQP_NMPC_SYNC set in the environment: the whole batch step by step, same
     results).  subproblem, xs_lin, xs_quad and shooting as in NMPC.solve (with 'multiple' the warm
     start also carries the states: x_k <- x_{k+1}, x_N stepped with the repeated last move).  Returns X (batch, steps + 1, 4), U (batch, steps), exitflag and iterations
-    (batch, steps), kernel_ms, launches and rounds, the SQP rounds the loop launched."""
+    (batch, steps), kernel_ms, launches and rounds, the SQP rounds the loop launched.
+    refs: a set-point schedule, absolute, (steps, 4) for the whole batch or (batch, steps, 4): step t
+    is solved with the set-point refs[t] (constant over the horizon; NMPC.linearize says how it enters
+    the cost); dist, same shapes: X[t + 1] = dynamic(delta, X[t], U[t]) + dist[t].  With either, the
+    loop is bqp_closed_loop_nmpc_track and the result also holds theta (batch, steps), the theta of
+    every step's solution; with neither it is bqp_closed_loop_nmpc, as before.  x_ref: a constant
+    set-point, (4,) or (batch, 4), for the steps no schedule covers."""
     lib = _lib.load()
     h = handle or _default_handle()
     xi = _f64(np.atleast_2d(x_init))
@@ -284,12 +331,25 @@ def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, p
     X = np.zeros((b, steps + 1, 4)); U = np.zeros((b, steps))
     fl = np.zeros((b, steps), np.int32); it = np.zeros((b, steps), np.int32)
     soft = prob._soft(xs_lin, xs_quad)
-    dims, dd = prob._dims(subproblem, shooting), prob._data(soft=soft)
+    xr = prob._ref(x_ref, b)
+    dims, dd = prob._dims(subproblem, shooting), prob._data(soft=soft, x_ref=xr)
     cl = ClosedLoop(_BQP_PLANT_MG_RK4, steps, prob.delta, _lib.ptr(prob.x_eq), _lib.ptr(prob.u_eq))
     o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
-    rc = lib.bqp_closed_loop_nmpc(h.value, C.byref(dims), b, C.byref(dd), C.byref(o), C.byref(cl),
-                                  _lib.ptr(xi), _lib.ptr(X), _lib.ptr(U), _lib.iptr(fl), _lib.iptr(it))
-    _lib.check(rc, 'bqp_closed_loop_nmpc')
+    r = OcpResult(X=X, U=U, exitflag=fl, iterations=it)
+    if refs is None and dist is None:
+        rc = lib.bqp_closed_loop_nmpc(h.value, C.byref(dims), b, C.byref(dd), C.byref(o), C.byref(cl),
+                                      _lib.ptr(xi), _lib.ptr(X), _lib.ptr(U), _lib.iptr(fl), _lib.iptr(it))
+        _lib.check(rc, 'bqp_closed_loop_nmpc')
+    else:
+        (ra, sr), (da, sd) = _schedule(refs, b, steps, 'refs'), _schedule(dist, b, steps, 'dist')
+        theta = np.zeros((b, steps))
+        tr = _lib.NmpcTrack(_lib.ptr(ra) if ra is not None else None, sr,
+                            _lib.ptr(da) if da is not None else None, sd, _lib.ptr(theta))
+        rc = lib.bqp_closed_loop_nmpc_track(h.value, C.byref(dims), b, C.byref(dd), C.byref(o), C.byref(cl),
+                                            _lib.ptr(xi), C.byref(tr), _lib.ptr(X), _lib.ptr(U),
+                                            _lib.iptr(fl), _lib.iptr(it))
+        _lib.check(rc, 'bqp_closed_loop_nmpc_track')
+        r.update(theta=theta)
     ms, launches = h.kernel_ms()
-    return OcpResult(X=X, U=U, exitflag=fl, iterations=it, kernel_ms=ms, launches=launches,
-                     rounds=h.loop_rounds())
+    r.update(kernel_ms=ms, launches=launches, rounds=h.loop_rounds())
+    return r

@@ -1522,6 +1522,7 @@ static int nmpc_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
         return BQP_E_ARG;
     if (d->subproblem != 0 && d->subproblem != 1) return BQP_E_ARG;
     if (d->shooting != 0 && d->shooting != 1) return BQP_E_ARG;
+    if (D->x_ref && D->sx_ref < 0) return BQP_E_ARG;
     if (!bqp::nmpc_supported(d->N, d->mx, d->mu)) return BQP_E_UNSUPPORTED;
     // multiple shooting lives on the stage route: its sub-problem is the stage QP with defects
     if (d->shooting == 1 && d->subproblem != 1) return BQP_E_UNSUPPORTED;
@@ -1531,6 +1532,31 @@ static int nmpc_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
     if (d->subproblem == 1 && bqp::ocp_rpl_for(std::max(d->n_poly, 1)) < 0) return BQP_E_UNSUPPORTED;
     return BQP_OK;
 }
+
+// the set-point of D (bqp_nmpc_data.x_ref) as the launchers take it: null without one, and then
+// every launch is the one it was before the member existed
+struct NmpcRef {
+    bqp::NmpcRefArgs r;
+    explicit NmpcRef(const bqp_nmpc_data* D) : r{D->x_ref, D->sx_ref} {}
+    const bqp::NmpcRefArgs* p() const { return r.xref ? &r : nullptr; }
+    // Dense route with a set-point.  The dense interior-point sub-problem stops at a stationarity of
+    // tol (1 + |f|), and the set-point adds g = -2 rho'T LAMBDA to f[N]: 1.9e3 for a target outside
+    // the terminal set (rho = 2 LAMBDA, T = 1000 I).  There theta sits on a terminal row with a
+    // multiplier of 7.6e2, the interior point stalls at a residual of 6.8e-6 - inside that bound at
+    // the default 1e-8, so it reports convergence - and the smallest curvature over the moves (0.52)
+    // turns it into 5.0e-6 in u_0 at N = 10, which the SQP then returns with flag 1.  Measured on
+    // that sub-problem alone: the interior point does not get below the 5.0e-6 at any tolerance; the
+    // active-set polish, reached once the tolerance makes it give up, is exact (3.6e-16).  So with a
+    // set-point the sub-problems are held to 1e-2 of the caller's tolerance (1e-10 at the default;
+    // at 1e-11 well-conditioned sub-problems of the same cases no longer end 1), and where the
+    // caller leaves polish at its default 0 a sub-problem that ends 0 / -8 is polished (mode 1).
+    // polish < 0 keeps it off.  Every other sub-problem measured ends 1 in the iterations it took
+    // before (7-14), with the same error.
+    void sharpen(bqp::DenseKernelArgs& q, const bqp_options& o) const {
+        if (r.xref) q.tol_stat = std::min(q.tol_stat, 1e-2 * o.tol_stat);
+    }
+    int polish(const bqp_options& o) const { return (r.xref && o.polish == 0) ? 1 : 0; }
+};
 
 // the SQP's kernel arguments over the handle's nwork (done, ndone and the penalty zeroed) and
 // the dense-kernel arguments of its sub-problem with the instance's own C; C, H, f: the
@@ -1613,15 +1639,17 @@ int bqp_nmpc_linearize_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     a.z = const_cast<double*>(z);       // read only by the rollout
     ne.z = a.z;
     a.Xout = X; a.cout = c;
-    HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st));
+    const NmpcRef ref(D);
+    HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st, nullptr, ref.p()));
     if (H || f) HIP_TRY(bqp::launch_lbmpc_normal(ne, st));
     if (cost) HIP_TRY(hipMemcpyAsync(cost, a.cost0, sizeof(double) * batch, hipMemcpyDeviceToDevice, st));
     return BQP_OK;
 }
 
 // registers the shared problem data of D with the stage; after st.commit() *Dd holds the device
-// copies (x0 is the caller's to set)
-static void stage_nmpc_data(Stage& st, const bqp_nmpc_dims* d, const bqp_nmpc_data* D, bqp_nmpc_data* Dd) {
+// copies (x0 is the caller's to set); the set-points of the batch's instances with them
+static void stage_nmpc_data(Stage& st, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                            bqp_nmpc_data* Dd) {
     const size_t mx = d->mx, mu = d->mu, mp = d->n_poly;
     *Dd = *D;
     st.in(&Dd->Lq, D->Lq, 16);          st.in(&Dd->Lr, D->Lr, 1);
@@ -1632,6 +1660,7 @@ static void stage_nmpc_data(Stage& st, const bqp_nmpc_dims* d, const bqp_nmpc_da
     st.in(&Dd->F_u, D->F_u, mu);        st.in(&Dd->h_u, D->h_u, mu);
     st.in(&Dd->F_T, D->F_T, 5 * mp);    st.in(&Dd->h_T, D->h_T, mp);
     st.in(&Dd->xs_lin, D->xs_lin, mx);  st.in(&Dd->xs_quad, D->xs_quad, mx);
+    st.in(&Dd->x_ref, D->x_ref, span(batch, D->sx_ref, 4));
 }
 
 // soft state rows (bqp_nmpc_data.xs_lin / xs_quad): a weight array is given
@@ -1642,13 +1671,23 @@ static int nmpc_soft_check(const bqp_nmpc_dims* d, const bqp_nmpc_data* D) {
     return (nmpc_soft(D) && d->subproblem != 1) ? BQP_E_UNSUPPORTED : BQP_OK;
 }
 
-// host entry points: every weight finite and >= 0 (the device entries leave that to the caller)
-static int nmpc_soft_host_check(const bqp_nmpc_dims* d, const bqp_nmpc_data* D) {
+// every entry of a per-instance array of `per` doubles (stride 0: one block for the batch) finite
+static bool nmpc_all_finite(const double* p, int batch, int64_t stride, size_t per) {
+    if (!p) return true;
+    for (int b = 0; b < (stride == 0 ? 1 : batch); ++b)
+        for (size_t i = 0; i < per; ++i)
+            if (!std::isfinite(p[(int64_t)b * stride + i])) return false;
+    return true;
+}
+
+// host entry points: every weight finite and >= 0, every set-point finite (the device entries leave
+// that to the caller)
+static int nmpc_host_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D) {
     for (const double* w : {D->xs_lin, D->xs_quad})
         if (w)
             for (int i = 0; i < d->mx; ++i)
                 if (!(w[i] >= 0.0) || !std::isfinite(w[i])) return BQP_E_ARG;
-    return BQP_OK;
+    return nmpc_all_finite(D->x_ref, batch, D->sx_ref, 4) ? BQP_OK : BQP_E_ARG;
 }
 
 // Stage route (bqp_nmpc_dims.subproblem = 1): the SQP's kernel arguments over the handle's nwork
@@ -1670,6 +1709,9 @@ struct NmpcStageRoute {
     bool soft;
     bqp::NmpcSoftArgs q;
     const bqp::NmpcSoftArgs* softp() const { return soft ? &q : nullptr; }
+    // the set-point (bqp_nmpc_data.x_ref): null without one
+    bqp::NmpcRefArgs r;
+    const bqp::NmpcRefArgs* refp() const { return r.xref ? &r : nullptr; }
     // multiple shooting (bqp_nmpc_dims.shooting = 1): the states of the iterate over the workspace's
     // Xw (the callers put their own array there), c_k = the defects, pi requested from the solve
     bool dms;
@@ -1701,6 +1743,7 @@ static int nmpc_stage_setup(bqp_handle h, const bqp_nmpc_dims* d, int batch, con
     a.xeq = D->x_eq; a.ueq = D->u_eq; a.Fx = D->F_x; a.hx = D->h_x; a.Fu = D->F_u; a.hu = D->h_u;
     a.FT = D->F_T; a.hT = D->h_T;
     a.x0 = D->x0; a.sx0 = D->sx0;
+    R.r = NmpcRef(D).r;
     a.f = layout::at<double>(nw, NL.f);
     a.ctl = layout::at<double>(nw, NL.ctl);
     a.rhs = layout::at<double>(nw, NL.rhs);
@@ -1825,8 +1868,8 @@ static int nmpc_stage_round(bqp_handle h, const NmpcStageRoute& R, hipStream_t s
         return BQP_OK;
     };
     BQP_TRY(mark(0));
-    if (R.dms) HIP_TRY(bqp::launch_nmpc_dms_linearize(R.a, R.s, R.m, st));
-    else HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st, R.softp()));
+    if (R.dms) HIP_TRY(bqp::launch_nmpc_dms_linearize(R.a, R.s, R.m, st, R.refp()));
+    else HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st, R.softp(), R.refp()));
     BQP_TRY(mark(1));
     BQP_TRY(bqp_solve_ocp_batched_device(h, &R.od, R.a.batch, &R.oD, &R.qo, R.xo, R.uo, R.tho, R.fv, R.sflag,
                                          nullptr, &R.du, st));
@@ -1835,7 +1878,7 @@ static int nmpc_stage_round(bqp_handle h, const NmpcStageRoute& R, hipStream_t s
     if (R.dms) {
         HIP_TRY(bqp::launch_nmpc_dms_backmap(R.a, R.s, R.m, st));
         BQP_TRY(mark(3));
-        HIP_TRY(bqp::launch_nmpc_dms_trial(R.a, R.m, st));
+        HIP_TRY(bqp::launch_nmpc_dms_trial(R.a, R.m, st, R.refp()));
         BQP_TRY(mark(4));
         HIP_TRY(bqp::launch_nmpc_dms_update(R.a, R.m, st));
         BQP_TRY(mark(5));
@@ -1844,7 +1887,7 @@ static int nmpc_stage_round(bqp_handle h, const NmpcStageRoute& R, hipStream_t s
     }
     HIP_TRY(bqp::launch_nmpc_stage_backmap(R.a, R.s, st, R.softp()));
     BQP_TRY(mark(3));
-    HIP_TRY(bqp::launch_nmpc_rollout(R.a, 0, st, R.softp()));
+    HIP_TRY(bqp::launch_nmpc_rollout(R.a, 0, st, R.softp(), R.refp()));
     BQP_TRY(mark(4));
     HIP_TRY(bqp::launch_nmpc_update(R.a, st, R.softp()));
     BQP_TRY(mark(5));
@@ -1937,7 +1980,7 @@ int bqp_nmpc_stage_qp_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     NmpcStageRoute R;
     BQP_TRY(nmpc_stage_setup(h, d, batch, D, o, st, R, &user, false));
     R.a.z = const_cast<double*>(z);     // read only by the rollout
-    HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st));
+    HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, st, nullptr, R.refp()));
     return BQP_OK;
 }
 
@@ -1946,7 +1989,7 @@ int bqp_nmpc_stage_cost(bqp_handle h, const bqp_nmpc_dims* d, int batch, const b
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_check(d, batch, D, true));
     if (!z) return BQP_E_ARG;
-    BQP_TRY(nmpc_soft_host_check(d, D));
+    BQP_TRY(nmpc_host_check(d, batch, D));
     if (bqp::ocp_rpl_for(std::max(d->n_poly, 1)) < 0) return BQP_E_UNSUPPORTED;
     DevScope ds(h->device);
     const size_t Bt = batch, N = d->N;
@@ -1954,7 +1997,7 @@ int bqp_nmpc_stage_cost(bqp_handle h, const bqp_nmpc_dims* d, int batch, const b
     bqp_nmpc_data Dd;
     const double* zd;
     double *cd = nullptr, *pd = nullptr;
-    stage_nmpc_data(st, d, D, &Dd);
+    stage_nmpc_data(st, d, batch, D, &Dd);
     st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
     st.in(&zd, z, Bt * (N + 1));
     st.out(&cd, Bt, cost);
@@ -1965,7 +2008,7 @@ int bqp_nmpc_stage_cost(bqp_handle h, const bqp_nmpc_dims* d, int batch, const b
     NmpcStageRoute R;
     BQP_TRY(nmpc_stage_setup(h, d, batch, &Dd, o, h->stream, R));
     R.a.z = const_cast<double*>(zd);    // read only by the rollout
-    HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, h->stream, R.softp()));
+    HIP_TRY(bqp::launch_nmpc_stage_rollout(R.a, R.s, h->stream, R.softp(), R.refp()));
     HIP_TRY(hipMemcpyAsync(cd, R.a.cost0, sizeof(double) * Bt, hipMemcpyDeviceToDevice, h->stream));
     if (R.soft) HIP_TRY(hipMemcpyAsync(pd, R.q.pen0, sizeof(double) * Bt, hipMemcpyDeviceToDevice, h->stream));
     else HIP_TRY(hipMemsetAsync(pd, 0, sizeof(double) * Bt, h->stream));
@@ -1978,7 +2021,7 @@ int bqp_nmpc_stage_qp(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_check(d, batch, D, true));
     if (!z) return BQP_E_ARG;
-    BQP_TRY(nmpc_soft_host_check(d, D));
+    BQP_TRY(nmpc_host_check(d, batch, D));
     DevScope ds(h->device);
     const size_t Bt = batch, N = d->N, mp = d->n_poly;
     Stage st(h);
@@ -1986,7 +2029,7 @@ int bqp_nmpc_stage_qp(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp
     const double* zd;
     double *Ad = nullptr, *Bd = nullptr, *wd = nullptr, *xld = nullptr, *xud = nullptr, *uld = nullptr,
            *uud = nullptr, *hpd = nullptr, *Wd = nullptr, *Fpd = nullptr;
-    stage_nmpc_data(st, d, D, &Dd);
+    stage_nmpc_data(st, d, batch, D, &Dd);
     st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
     st.in(&zd, z, Bt * (N + 1));
     if (A) st.out(&Ad, Bt * N * 16, A);
@@ -2012,14 +2055,14 @@ int bqp_nmpc_linearize(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bq
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_check(d, batch, D, true));
     if (!z) return BQP_E_ARG;
-    BQP_TRY(nmpc_soft_host_check(d, D));
+    BQP_TRY(nmpc_host_check(d, batch, D));
     DevScope ds(h->device);
     const size_t B = batch, N = d->N, n = N + 1, m = N * (size_t)(d->mx + d->mu) + d->n_poly;
     Stage st(h);
     bqp_nmpc_data Dd;
     const double* zd;
     double *Xd = nullptr, *cd = nullptr, *cvd = nullptr, *Cd = nullptr, *Hd = nullptr, *fd = nullptr;
-    stage_nmpc_data(st, d, D, &Dd);
+    stage_nmpc_data(st, d, batch, D, &Dd);
     st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
     st.in(&zd, z, B * n);
     if (X) st.out(&Xd, B * (N + 1) * 4, X);
@@ -2051,6 +2094,8 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
     bqp::LbmpcArgs ne;
     bqp::DenseKernelArgs q;
     HIP_TRY(nmpc_setup(h, d, batch, D, o, nullptr, nullptr, nullptr, st, a, ne, &q));
+    const NmpcRef ref(D);
+    ref.sharpen(q, o);
     a.z = z; ne.z = z; a.flag = exitflag; a.iters = iterations;
     if (lam) { a.lam = lam; q.lam_ineqlin = lam; }
     HIP_TRY(hipMemsetAsync(a.iters, 0, sizeof(int) * B, st));
@@ -2080,9 +2125,9 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
         // ended -8 that way).  The interior-point iterate of those sub-problems (exit -8 once
         // mu ~ 1e-15, which the update kernel takes as is) is accurate: the same solves converge
         // in 2-3 SQP iterations without the polish.
-        q.polish = o.polish > 0 ? sub_polish(o.polish, it >= LB_POLISH_STALL) : 0;
+        q.polish = o.polish > 0 ? sub_polish(o.polish, it >= LB_POLISH_STALL) : ref.polish(o);
         BQP_TRY(mark(0));
-        HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st));
+        HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st, nullptr, ref.p()));
         BQP_TRY(mark(1));
         HIP_TRY(bqp::launch_lbmpc_normal(ne, st));
         BQP_TRY(mark(2));
@@ -2102,7 +2147,7 @@ int bqp_nmpc_solve_batched_device(bqp_handle h, const bqp_nmpc_dims* d, int batc
                 fprintf(stderr, "bqp nmpc it %d instance %zu: sub-problem flag %d, |d| %.3e\n", it, b, fl[b], dm);
             }
         }
-        HIP_TRY(bqp::launch_nmpc_rollout(a, 0, st));
+        HIP_TRY(bqp::launch_nmpc_rollout(a, 0, st, nullptr, ref.p()));
         BQP_TRY(mark(4));
         HIP_TRY(bqp::launch_nmpc_update(a, st));
         BQP_TRY(mark(5));
@@ -2136,7 +2181,7 @@ int bqp_nmpc_solve_batched(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_check(d, batch, D, true));
     if (!z || !exitflag || !iterations) return BQP_E_ARG;
-    BQP_TRY(nmpc_soft_host_check(d, D));
+    BQP_TRY(nmpc_host_check(d, batch, D));
     BQP_TRY(nmpc_soft_check(d, D));
     DevScope ds(h->device);
     const size_t B = batch, N = d->N, n = N + 1, m = N * (size_t)(d->mx + d->mu) + d->n_poly;
@@ -2144,7 +2189,7 @@ int bqp_nmpc_solve_batched(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     bqp_nmpc_data Dd;
     double *zd, *ld, *cd;
     int *ed, *itd;
-    stage_nmpc_data(st, d, D, &Dd);
+    stage_nmpc_data(st, d, batch, D, &Dd);
     st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
     st.in(&zd, z, B * n, z);   // the initial iterate, and the solution
     st.out(&ld, B * m, lam);
@@ -2179,7 +2224,7 @@ int bqp_nmpc_dms_solve_batched(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_check(d, batch, D, true));
     if (!z || !exitflag || !iterations || d->shooting != 1) return BQP_E_ARG;
-    BQP_TRY(nmpc_soft_host_check(d, D));
+    BQP_TRY(nmpc_host_check(d, batch, D));
     BQP_TRY(nmpc_soft_check(d, D));
     DevScope ds(h->device);
     const size_t B = batch, N = d->N, n = N + 1, m = N * (size_t)(d->mx + d->mu) + d->n_poly;
@@ -2187,7 +2232,7 @@ int bqp_nmpc_dms_solve_batched(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     bqp_nmpc_data Dd;
     double *zd, *Xd = nullptr, *ld, *pd, *cd;
     int *ed, *itd;
-    stage_nmpc_data(st, d, D, &Dd);
+    stage_nmpc_data(st, d, batch, D, &Dd);
     st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
     st.in(&zd, z, B * n, z);   // the initial iterate, and the solution
     st.in(&Xd, X, B * n * 4, X);
@@ -2225,7 +2270,7 @@ int bqp_nmpc_dms_qp_device(bqp_handle h, const bqp_nmpc_dims* d, int batch, cons
     // the states into the workspace's copy (the linearisation pins its stage 0 to the measured state)
     if (X) HIP_TRY(hipMemcpyAsync(R.m.X, X, sizeof(double) * batch * 4 * (size_t)(d->N + 1), hipMemcpyDeviceToDevice, st));
     else HIP_TRY(bqp::launch_nmpc_dms_start(R.a, R.m, st));
-    HIP_TRY(bqp::launch_nmpc_dms_linearize(R.a, R.s, R.m, st));
+    HIP_TRY(bqp::launch_nmpc_dms_linearize(R.a, R.s, R.m, st, R.refp()));
     return BQP_OK;
 }
 
@@ -2235,7 +2280,7 @@ int bqp_nmpc_dms_qp(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_n
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_check(d, batch, D, true));
     if (!z) return BQP_E_ARG;
-    BQP_TRY(nmpc_soft_host_check(d, D));
+    BQP_TRY(nmpc_host_check(d, batch, D));
     DevScope ds(h->device);
     const size_t Bt = batch, N = d->N, mp = d->n_poly;
     Stage st(h);
@@ -2243,7 +2288,7 @@ int bqp_nmpc_dms_qp(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_n
     const double *zd, *Xd = nullptr;
     double *Ad = nullptr, *Bd = nullptr, *cd = nullptr, *wd = nullptr, *xld = nullptr, *xud = nullptr,
            *uld = nullptr, *uud = nullptr, *hpd = nullptr, *Wd = nullptr, *Fpd = nullptr;
-    stage_nmpc_data(st, d, D, &Dd);
+    stage_nmpc_data(st, d, batch, D, &Dd);
     st.in(&Dd.x0, D->x0, span(batch, D->sx0, 4));
     st.in(&zd, z, Bt * (N + 1));
     st.in(&Xd, X, Bt * (N + 1) * 4);
@@ -2275,12 +2320,23 @@ static int nmpc_loop_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_dat
     return nmpc_soft_check(d, D);
 }
 
-int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
-                                const bqp_nmpc_data* D, const bqp_options* opt,
-                                const bqp_closed_loop* cl, const double* x_init, double* X,
-                                double* U, int* exitflag, int* iterations, void* stream) {
+// a schedule's stride: 0 (shared by the batch) or at least one instance's steps * 4
+static int nmpc_track_check(const bqp_nmpc_track* tr, int steps) {
+    if (!tr) return BQP_OK;
+    for (int64_t sd : {tr->ref ? tr->sref : 0, tr->dist ? tr->sdist : 0})
+        if (sd != 0 && sd < (int64_t)steps * 4) return BQP_E_ARG;
+    return BQP_OK;
+}
+
+// bqp_closed_loop_nmpc_device (tr null: every launch is that loop's own) and
+// bqp_closed_loop_nmpc_track_device
+static int nmpc_loop_device(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                            const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,
+                            const bqp_nmpc_track* tr, double* X, double* U, int* exitflag, int* iterations,
+                            void* stream) {
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_loop_check(d, batch, D, cl, x_init, X, U));
+    BQP_TRY(nmpc_track_check(tr, cl->steps));
     DevScope ds(h->device);
     hipStream_t st = (hipStream_t)stream;
     const int N = d->N, n = N + 1, S = cl->steps;
@@ -2289,8 +2345,18 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     // reference in tests/test_gpu_nmpc_async.py, and the path BQP_LB_TRACE reports on)
     const bool sync_loop = getenv("BQP_NMPC_SYNC") != nullptr;
     const bool dms = d->shooting == 1;
-    const layout::CworkNmpc CL(batch, n, !sync_loop, dms);
+    // a track with nothing in it is no track; a schedule replaces data->x_ref step by step
+    const bool track = tr && S > 0 && (tr->ref || tr->dist || tr->THETA);
+    const bool sched = track && tr->ref;
+    const layout::CworkNmpc CL(batch, n, !sync_loop, dms, sched && !sync_loop);
     HIP_TRY(h->cwork.reserve(CL.bytes));
+    bqp::NmpcTrackArgs k;
+    memset(&k, 0, sizeof(k));
+    if (track) {
+        k.ref = tr->ref; k.sref = tr->ref ? tr->sref : 0;
+        k.dist = tr->dist; k.sdist = tr->dist ? tr->sdist : 0;
+        k.THETA = tr->THETA;
+    }
     double* s = layout::at<double>(h->cwork.p, CL.s);
     double* z = layout::at<double>(h->cwork.p, CL.z);
     int* fl = layout::at<int>(h->cwork.p, CL.flags);
@@ -2298,11 +2364,25 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     double* Xit = dms ? layout::at<double>(h->cwork.p, CL.Xit) : nullptr;   // the iterate's states
     HIP_TRY(bqp::launch_closed_loop_init(batch, 4, S, x_init, cl->x_eq, s, X, st));
     HIP_TRY(hipMemsetAsync(z, 0, sizeof(double) * B * n, st));   // cold start: u = u_eq, theta = 0
+    bqp_nmpc_data Dl = *D;
+    if (sched && !sync_loop) {
+        // the set-point each instance is at, kept as x0 is: step 0's here, the advance copies the rest
+        k.xr = layout::at<double>(h->cwork.p, CL.xr);
+        HIP_TRY(bqp::launch_nmpc_track_init(batch, k, st));
+        Dl.x_ref = k.xr;
+        Dl.sx_ref = 4;
+    }
     EventGuard e0;
     HIP_TRY(hipEventCreate(&e0.e));
     HIP_TRY(hipEventRecord(e0.e, st));
     int launches = 0, rounds = 0;
-    bqp_nmpc_data Dl = *D;
+    // the arguments of the advance (asynchronous) and of the track's plant launch (step-synchronous)
+    bqp::NmpcAdvanceArgs v;
+    memset(&v, 0, sizeof(v));
+    v.batch = batch; v.N = N; v.steps = S; v.plant = cl->plant; v.delta = cl->delta;
+    v.xeq = cl->x_eq; v.ueq = cl->u_eq;
+    v.s = s; v.z = z; v.X = X; v.U = U; v.iters = it; v.flag = fl;
+    v.flags = exitflag; v.itlog = iterations;
     if (!sync_loop && S > 0) {
         // asynchronous: every instance runs at its own closed-loop step.  Each round is one SQP
         // iteration of every unfinished instance, then nmpc_loop_advance_kernel moves the instances
@@ -2346,23 +2426,22 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
         q.polish = o.polish > 0 ? sub_polish(o.polish, false) : 0;
         q.pol_it = o.polish > 0 ? a.iters : nullptr;
         q.pol_stall = LB_POLISH_STALL;
-        bqp::NmpcAdvanceArgs v;
-        memset(&v, 0, sizeof(v));
-        v.batch = batch; v.N = N; v.steps = S; v.plant = cl->plant; v.delta = cl->delta;
-        v.xeq = cl->x_eq; v.ueq = cl->u_eq;
-        v.s = s; v.z = z; v.x0 = x0; v.X = X; v.U = U; v.nu = a.nu;
-        v.done = a.done; v.iters = it; v.flag = fl; v.ts = ts; v.nfin = nfin;
-        v.flags = exitflag; v.itlog = iterations;
+        v.x0 = x0; v.nu = a.nu; v.done = a.done; v.ts = ts; v.nfin = nfin;
+        const NmpcRef ref(&Dl);
+        if (!stage) {                    // dense route with a set-point: NmpcRef::sharpen
+            ref.sharpen(q, o);
+            if (o.polish <= 0) q.polish = ref.polish(o);
+        }
         // an instance stops within max_iter rounds of its step's first: the bound is never reached
         const int64_t max_rounds = (int64_t)S * o.max_iter;
         for (int64_t r = 0; r < max_rounds; ++r) {
             if (stage) {
                 BQP_TRY(nmpc_stage_round(h, R, st, &launches));
             } else {
-                HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st));
+                HIP_TRY(bqp::launch_nmpc_rollout(a, 1, st, nullptr, ref.p()));
                 HIP_TRY(bqp::launch_lbmpc_normal(ne, st));
                 HIP_TRY(bqp::launch_dense(q, st));
-                HIP_TRY(bqp::launch_nmpc_rollout(a, 0, st));
+                HIP_TRY(bqp::launch_nmpc_rollout(a, 0, st, nullptr, ref.p()));
                 HIP_TRY(bqp::launch_nmpc_update(a, st));
                 launches += 5;
             }
@@ -2370,7 +2449,7 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
                 HIP_TRY(bqp::launch_nmpc_dms_loop_states(batch, N, S, D->delta, D->u_eq, z, Xit, a.done, ts, st));
                 launches += 1;
             }
-            HIP_TRY(bqp::launch_nmpc_loop_advance(v, st));
+            HIP_TRY(bqp::launch_nmpc_loop_advance(v, st, track ? &k : nullptr));
             launches += 1;
             ++rounds;
             int nf = 0;
@@ -2382,6 +2461,10 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     for (int t = 0; t < (sync_loop ? S : 0); ++t) {
         Dl.x0 = X + (int64_t)t * 4;      // the measured states X[:, t], absolute
         Dl.sx0 = (int64_t)(S + 1) * 4;
+        if (sched) {                     // the set-points ref[:, t]
+            Dl.x_ref = k.ref + (int64_t)t * 4;
+            Dl.sx_ref = k.sref;
+        }
         if (dms) {
             bqp_options o;
             resolve(opt, &o);
@@ -2391,9 +2474,11 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
         }
         launches += h->launches;
         rounds += h->nmpc_rounds;
-        // the plant reads u_0 - u_eq = z[b, 0] (stride n)
-        HIP_TRY(bqp::launch_mg_plant(cl->plant, batch, n, S, t, cl->delta, z, fl, cl->x_eq, cl->u_eq,
-                                     s, X, U, exitflag, st));
+        // the plant reads u_0 - u_eq = z[b, 0] (stride n); a track's plant launch also adds the
+        // disturbance and logs theta
+        if (track) HIP_TRY(bqp::launch_nmpc_track_plant(v, k, t, st));
+        else HIP_TRY(bqp::launch_mg_plant(cl->plant, batch, n, S, t, cl->delta, z, fl, cl->x_eq, cl->u_eq,
+                                          s, X, U, exitflag, st));
         if (dms) {
             HIP_TRY(bqp::launch_nmpc_dms_loop_states(batch, N, S, D->delta, D->u_eq, z, Xit, nullptr, nullptr, st));
             launches += 1;
@@ -2410,12 +2495,69 @@ int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
     return BQP_OK;
 }
 
+int bqp_closed_loop_nmpc_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                                const bqp_nmpc_data* D, const bqp_options* opt,
+                                const bqp_closed_loop* cl, const double* x_init, double* X,
+                                double* U, int* exitflag, int* iterations, void* stream) {
+    return nmpc_loop_device(h, d, batch, D, opt, cl, x_init, nullptr, X, U, exitflag, iterations, stream);
+}
+
+int bqp_closed_loop_nmpc_track_device(bqp_handle h, const bqp_nmpc_dims* d, int batch,
+                                      const bqp_nmpc_data* D, const bqp_options* opt,
+                                      const bqp_closed_loop* cl, const double* x_init,
+                                      const bqp_nmpc_track* tr, double* X, double* U, int* exitflag,
+                                      int* iterations, void* stream) {
+    return nmpc_loop_device(h, d, batch, D, opt, cl, x_init, tr, X, U, exitflag, iterations, stream);
+}
+
+int bqp_closed_loop_nmpc_track(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
+                               const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,
+                               const bqp_nmpc_track* tr, double* X, double* U, int* exitflag,
+                               int* iterations) {
+    if (!h) return BQP_E_ARG;
+    BQP_TRY(nmpc_loop_check(d, batch, D, cl, x_init, X, U));
+    BQP_TRY(nmpc_track_check(tr, cl->steps));
+    BQP_TRY(nmpc_host_check(d, batch, D));
+    const size_t B = batch, S = cl->steps;
+    if (tr && (!nmpc_all_finite(tr->ref, batch, tr->sref, S * 4) ||
+               !nmpc_all_finite(tr->dist, batch, tr->sdist, S * 4)))
+        return BQP_E_ARG;
+    DevScope ds(h->device);
+    Stage st(h);
+    bqp_nmpc_data Dd;
+    bqp_closed_loop cd = *cl;
+    bqp_nmpc_track td;
+    memset(&td, 0, sizeof(td));
+    const double* xi;
+    double *Xd, *Ud, *Td = nullptr;
+    int *Fd, *Id;
+    stage_nmpc_data(st, d, batch, D, &Dd);
+    st.in(&xi, x_init, B * 4);
+    st.in(&cd.x_eq, cl->x_eq, 4);
+    st.in(&cd.u_eq, cl->u_eq, 1);
+    if (tr) {
+        td.sref = tr->sref; td.sdist = tr->sdist;
+        st.in(&td.ref, tr->ref, span(batch, tr->sref, S * 4));
+        st.in(&td.dist, tr->dist, span(batch, tr->sdist, S * 4));
+        if (tr->THETA) st.out(&Td, B * S, tr->THETA);
+    }
+    st.out(&Xd, B * (S + 1) * 4, X);
+    st.out(&Ud, B * S, U);
+    st.out(&Fd, B * S, exitflag);
+    st.out(&Id, B * S, iterations);
+    BQP_TRY(st.commit());
+    td.THETA = Td;
+    BQP_TRY(nmpc_loop_device(h, d, batch, &Dd, opt, &cd, xi, tr ? &td : nullptr, Xd, Ud,
+                             exitflag ? Fd : nullptr, iterations ? Id : nullptr, h->stream));
+    return st.finish();
+}
+
 int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* D,
                          const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,
                          double* X, double* U, int* exitflag, int* iterations) {
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_loop_check(d, batch, D, cl, x_init, X, U));
-    BQP_TRY(nmpc_soft_host_check(d, D));
+    BQP_TRY(nmpc_host_check(d, batch, D));
     DevScope ds(h->device);
     const size_t B = batch, S = cl->steps;
     Stage st(h);
@@ -2424,7 +2566,7 @@ int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const 
     const double* xi;
     double *Xd, *Ud;
     int *Fd, *Id;
-    stage_nmpc_data(st, d, D, &Dd);
+    stage_nmpc_data(st, d, batch, D, &Dd);
     st.in(&xi, x_init, B * 4);
     st.in(&cd.x_eq, cl->x_eq, 4);
     st.in(&cd.u_eq, cl->u_eq, 1);

@@ -225,18 +225,28 @@ struct NmpcDmsArgs {
     const double* pi;          // batch x 4 N: the structured solve's pi
     double *sw, *gn, *pimax;   // batch each: sum w_k'v_k, |grad J|, max |pi|
 };
+// Set-point of the tracking cost (bqp_nmpc_data.x_ref): the offset term pulls LAMBDA theta to
+// rho = x_ref - x_eq, its four residual rows are (Lt LAMBDA) theta - Lt rho.  A separate, trailing
+// kernel argument of the kernels that evaluate that term, read by their reference instantiations
+// alone; the launchers take a null pointer for "the working point", and then launch the
+// instantiations that existed before the member did.
+struct NmpcRefArgs {
+    const double* xref;   // 4 per instance, absolute
+    int64_t sref;         // doubles between two instances' set-points; 0: one for the batch
+};
 bool nmpc_supported(int N, int mx, int mu);
 // multiple shooting: X = the rollout of z, for a solve that is given no states (once per solve)
 hipError_t launch_nmpc_dms_start(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st);
 // the linearisation at (X, z), lanes over the stages: A, B, c, w, bounds, hp, rhs, cost0
 hipError_t launch_nmpc_dms_linearize(const NmpcArgs& a, const NmpcStageArgs& s, const NmpcDmsArgs& m,
-                                     hipStream_t st);
+                                     hipStream_t st, const NmpcRefArgs* r = nullptr);
 // after the structured solve: d, lam in NMPC row order, qpflag, sum w_k'v_k, the full-space
 // stationarity residual (a.stat), |grad J|, max |pi|
 hipError_t launch_nmpc_dms_backmap(const NmpcArgs& a, const NmpcStageArgs& s, const NmpcDmsArgs& m,
                                    hipStream_t st);
 // the ntrial trial points (X, z) + 2^-t (dX, d): costT = J, violT = V + E
-hipError_t launch_nmpc_dms_trial(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st);
+hipError_t launch_nmpc_dms_trial(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st,
+                                 const NmpcRefArgs* r = nullptr);
 hipError_t launch_nmpc_dms_update(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st);
 // closed loop, after a step's solve and before the warm start of z: the warm start of the states,
 // x_k <- x_{k+1}, x_N <- dynamic(delta, x_N, u_{N-1}) with the repeated last move (x_0 is the next
@@ -251,14 +261,15 @@ hipError_t launch_nmpc_stage_table(const NmpcArgs& a, const NmpcStageArgs& s, hi
 // the rollout at z with the stage Jacobians: A, B, w, bounds, hp, rhs, cost0 (with q: pen0, and
 // cost0 = J + pen0)
 hipError_t launch_nmpc_stage_rollout(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
-                                     const NmpcSoftArgs* q = nullptr);
+                                     const NmpcSoftArgs* q = nullptr, const NmpcRefArgs* r = nullptr);
 // after the structured solve: d, lam in NMPC row order, qpflag, f and C'lam by the adjoint sweep
 // (with q: plin from the solve's slacks)
 hipError_t launch_nmpc_stage_backmap(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
                                      const NmpcSoftArgs* q = nullptr);
 // gn = 1: rollout with sensitivities at z (Jr, er, C, rhs, cost0); gn = 0: the ntrial trial points
 // (with q: costT = J + penalty, violT over the hard rows)
-hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st, const NmpcSoftArgs* q = nullptr);
+hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st, const NmpcSoftArgs* q = nullptr,
+                               const NmpcRefArgs* r = nullptr);
 // with q (stage route only): the hard rows' reductions and D = f'd + plin - pen0 - nu V0
 hipError_t launch_nmpc_update(const NmpcArgs& a, hipStream_t st, const NmpcSoftArgs* q = nullptr);
 // closed loop: after the plant step of step t, the step's SQP iteration counts into the log and
@@ -267,7 +278,14 @@ hipError_t launch_nmpc_loop_shift(int batch, int N, int steps, int t, double* z,
                                   int* itlog, hipStream_t st);
 // asynchronous closed loop (NmpcAdvanceArgs: bqp_nmpc_advance.h): after an SQP round, every instance
 // whose SQP has stopped logs its step, steps the plant and sets up its next solve
-hipError_t launch_nmpc_loop_advance(const NmpcAdvanceArgs& a, hipStream_t st);
+// k (bqp_closed_loop_nmpc_track): also theta into its log, the disturbance onto the plant's state
+// and the next step's set-point; null: the advance as it was
+hipError_t launch_nmpc_loop_advance(const NmpcAdvanceArgs& a, hipStream_t st, const NmpcTrackArgs* k = nullptr);
+// bqp_closed_loop_nmpc_track, once per loop: the set-points of step 0 into k.xr
+hipError_t launch_nmpc_track_init(int batch, const NmpcTrackArgs& k, hipStream_t st);
+// bqp_closed_loop_nmpc_track, step-synchronous loop: mg_plant_kernel's step t of every instance from
+// z[b, 0] with the disturbance added and theta logged (the advance's arithmetic, lane for lane)
+hipError_t launch_nmpc_track_plant(const NmpcAdvanceArgs& a, const NmpcTrackArgs& k, int t, hipStream_t st);
 
 // closed-loop simulation (bqp_plant.hip): Moore-Greitzer plant (RK4 step or MATLAB ode23,
 // BQP_PLANT_*) between batched solves

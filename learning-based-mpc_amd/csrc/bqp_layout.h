@@ -264,10 +264,12 @@ struct CworkSqp : Arena {
 // adds the instances' step counters, the count of finished instances - nfin follows ts directly:
 // one memset zeroes both - and the measured state in absolute coordinates (4 per instance, the
 // solve's x0); the step-synchronous loop's layout is unchanged by it.  Multiple shooting (dms) adds
-// the iterate's states (4 n per instance) after everything else
+// the iterate's states (4 n per instance) after everything else; a set-point schedule in the
+// asynchronous loop (track) then adds the set-point each instance is at (4 per instance, the
+// solve's x_ref), kept as x0 is
 struct CworkNmpc : Arena {
-    Region s, z, flags, iters, ts, nfin, x0, Xit;
-    CworkNmpc(size_t B, size_t n, bool own_step = false, bool dms = false) {
+    Region s, z, flags, iters, ts, nfin, x0, Xit, xr;
+    CworkNmpc(size_t B, size_t n, bool own_step = false, bool dms = false, bool track = false) {
         s = take<double>(B * 4);
         z = take<double>(B * n);
         flags = take<int>(B);
@@ -278,6 +280,7 @@ struct CworkNmpc : Arena {
             x0 = take<double>(B * 4);
         }
         if (dms) Xit = take<double>(B * n * 4);
+        if (track) xr = take<double>(B * 4);
     }
 };
 

@@ -1,7 +1,7 @@
 // bqp_mg.h — the Moore-Greitzer compressor of the reference's closed loops and its integrators
 // over one sampling period, shared by the kernels that step the true plant (bqp_plant.hip:
 // mg_plant_kernel, track_advance_kernel, sqp_loop_advance_kernel; bqp_nmpc.hip:
-// nmpc_loop_advance_kernel), so that every loop steps the plant with the same arithmetic
+// nmpc_loop_advance_kernel, nmpc_track_plant_kernel), so that every loop steps the plant with the same arithmetic
 // (mg_plant_step below).  Device code only.
 //
 // `system` of examples/DMS_tracking_LMPC_casadi.m:215-221 (the same model as

@@ -34,6 +34,11 @@
 //   nmpc_loop_shift_kernel      step-synchronous closed loop: the warm start of the next step
 //   nmpc_loop_advance_kernel    asynchronous closed loop, after every iteration: the instances
 //                               whose SQP has stopped move to their next closed-loop step
+// Set-points (bqp_nmpc_data.x_ref): the kernels that evaluate the T term - the rollouts, the stage
+// rollout, multiple shooting's linearisation and trials - have a REF instantiation each, which reads
+// the instance's set-point through a trailing NmpcRefArgs (NmLtRho).  The loop with a schedule
+// (bqp_closed_loop_nmpc_track): nmpc_loop_advance_kernel<true>, nmpc_track_init_kernel once per
+// loop, nmpc_track_plant_kernel in the step-synchronous loop.
 // Multiple shooting on the stage route (bqp_nmpc_dims.shooting = 1; the nmpc_dms_* kernels below) =
 // dms linearise -> structured solve with the defects as its per-stage offset -> dms back-map ->
 // dms trials -> dms update: the states stay variables, lanes run over the stages, no rollout in a round
@@ -152,11 +157,38 @@ __device__ __forceinline__ void nm_load_consts(const NmpcArgs& a, int lane, doub
     }
 }
 
+// REF instantiations (bqp_nmpc_data.x_ref): Lt rho for the set-point rho = x_ref - x_eq of instance
+// b, from the constant block in LDS.  Every lane forms it (the T term is wave-uniform work): 4
+// subtractions and 10 multiply-adds; the T rows are then (Lt LAMBDA) theta - Lt rho, so rho = 0
+// gives the values of the instantiations without a set-point.  Without REF the type is empty and row()
+// hands the product back: those instantiations keep their code
+template <bool REF> struct NmLtRho {
+    __device__ __forceinline__ NmLtRho(const NmpcRefArgs&, int, const double*) {}
+    __device__ __forceinline__ double row(double e, int) const { return e; }
+};
+template <> struct NmLtRho<true> {
+    double lt[4];
+    __device__ __forceinline__ NmLtRho(const NmpcRefArgs& rf, int b, const double* cst) {
+        double rho[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rho[i] = rf.xref[(int64_t)b * rf.sref + i] - cst[NO_XE + i];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            double v = 0.0;
+#pragma unroll
+            for (int c2 = r; c2 < 4; ++c2) v += cst[NO_T + 4 * r + c2] * rho[c2];
+            lt[r] = v;
+        }
+    }
+    __device__ __forceinline__ double row(double e, int r) const { return e - lt[r]; }
+};
+
 // SOFT (trial points of the stage route only): lane i < mx owns row i of F_x with its weights; a
 // softened row's max(c, 0) goes into the lane's penalty instead of V, costT = J + sum of the
-// penalties.  q is read by the SOFT instantiation alone.
-template <bool GN, bool SOFT = false>
-__global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a, NmpcSoftArgs q) {
+// penalties.  q is read by the SOFT instantiations alone, rf by the REF ones (the set-point of the T
+// term: NmLtRho).
+template <bool GN, bool SOFT = false, bool REF = false>
+__global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a, NmpcSoftArgs q, NmpcRefArgs rf) {
     static_assert(!(GN && SOFT), "the soft rows belong to the stage route: no linearisation here");
     const int lane = threadIdx.x;
     const int nt = GN ? 1 : a.ntrial;
@@ -319,14 +351,15 @@ __global__ void __launch_bounds__(64) nmpc_rollout_kernel(NmpcArgs a, NmpcSoftAr
 #pragma unroll
         for (int i = 0; i < 4; ++i) Xout[4 * N + i] = x[i];
     }
-    // terminal P on x_N, T on LAMBDA theta
+    // terminal P on x_N, T on LAMBDA theta (REF: on LAMBDA theta - rho)
     xresidual(NO_P, x);
+    const NmLtRho<REF> ltr(rf, b, cst);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
         double w = 0.0;
 #pragma unroll
         for (int c2 = r; c2 < 4; ++c2) w += cst[NO_T + 4 * r + c2] * cst[NO_L + c2];
-        const double e = w * th;
+        const double e = ltr.row(w * th, r);
         J += e * e;
         if (GN) {
             if (lane == 0) er[row + r] = e;
@@ -524,7 +557,12 @@ __global__ void __launch_bounds__(64) nmpc_loop_shift_kernel(int batch, int N, i
 // measured state for its next solve with the
 // per-solve state reset - per instance the operations of the step-synchronous loop in its order.
 // Every other wave leaves at once.  The indices are bqp_nmpc_advance.h's (checked on the host).
-__global__ void __launch_bounds__(64) nmpc_loop_advance_kernel(NmpcAdvanceArgs a) {
+// TRACK (bqp_closed_loop_nmpc_track; k is read by that instantiation alone): lane 0 also logs theta
+// of the step's solution, adds the step's disturbance to the plant's state - one addition after
+// mg_plant_step, rounded once: the state the log stores and the next solve measures - and, while
+// steps remain, copies the next step's set-point into the instance's slot of k.xr.
+template <bool TRACK>
+__global__ void __launch_bounds__(64) nmpc_loop_advance_kernel(NmpcAdvanceArgs a, NmpcTrackArgs k) {
     __shared__ double zs[NM_WAVE * NM_CPL];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= a.batch || !nmpc_advance_due(a, b)) return;   // uniform per wave
@@ -534,6 +572,9 @@ __global__ void __launch_bounds__(64) nmpc_loop_advance_kernel(NmpcAdvanceArgs a
     // every read of z (u_0, the shift's sources) and of the counters before the wave sync, every
     // write after it
     const double u0 = zb[0];
+    if constexpr (TRACK) {
+        if (lane == 0) nmpc_track_log(k, a.steps, N, b, t, zb);
+    }
     if (more)
         for (int j = lane; j < N; j += NM_WAVE) nmpc_shift_stage(zb, N, j, zs);
     wave_sync();
@@ -546,9 +587,45 @@ __global__ void __launch_bounds__(64) nmpc_loop_advance_kernel(NmpcAdvanceArgs a
         for (int i = 0; i < 4; ++i) x[i] = a.s[(int64_t)b * 4 + i] + a.xeq[i];
         const double u = u0 + a.ueq[0];
         mg_plant_step(a.plant, a.delta, x, u);
+        if constexpr (TRACK) {
+            nmpc_track_disturb(k, b, t, x);
+            nmpc_track_next_ref(k, a.steps, b, t);
+        }
         nmpc_advance_record(a, b, t, x, u);
         nmpc_advance_next(a, b, t);
     }
+}
+
+// bqp_closed_loop_nmpc_track, once per loop: the set-points of step 0 into the instances' slots
+__global__ void nmpc_track_init_kernel(int batch, NmpcTrackArgs k) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch * 4) return;
+    k.xr[i] = k.ref[nmpc_track_at(k.sref, i >> 2, 0, i & 3)];
+}
+
+// bqp_closed_loop_nmpc_track, step-synchronous loop: step t of every instance, one thread each -
+// what lane 0 of nmpc_loop_advance_kernel<true> does with the plant (the same inlined mg_plant_step,
+// the same single addition) and with the logs, from the solve's flags; the warm start and the
+// iteration log stay nmpc_loop_shift_kernel's, the set-point is the host's pointer into the schedule
+__global__ void nmpc_track_plant_kernel(NmpcAdvanceArgs a, NmpcTrackArgs k, int t) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.batch) return;
+    const double* zb = a.z + (int64_t)b * (a.N + 1);
+    nmpc_track_log(k, a.steps, a.N, b, t, zb);
+    double x[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = a.s[(int64_t)b * 4 + i] + a.xeq[i];
+    const double u = zb[0] + a.ueq[0];
+    mg_plant_step(a.plant, a.delta, x, u);
+    nmpc_track_disturb(k, b, t, x);
+    double* Xn = a.X + ((int64_t)b * (a.steps + 1) + t + 1) * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        a.s[(int64_t)b * 4 + i] = x[i] - a.xeq[i];
+        Xn[i] = x[i];
+    }
+    a.U[(int64_t)b * a.steps + t] = u;
+    if (a.flags) a.flags[(int64_t)b * a.steps + t] = a.flag[b];
 }
 
 // ------------------------------------------------------------------------------------------
@@ -636,8 +713,10 @@ template <> struct NmMapOf<true> { typedef NmpcBoundMap type; };
 // stage (rhs = -c) and the bound it stands for, lanes over the rows of F_T the terminal rhs and hp.
 // SOFT: lane i < mx also sums its row's penalty phi_i(max(c, 0)) over the stages; one wave sum gives
 // pen0, and cost0 = J + pen0.  The bounds stay as they are: the structured solve softens them.
-template <bool SOFT>
-__global__ void __launch_bounds__(64) nmpc_stage_rollout_kernel(NmpcArgs a, NmpcStageArgs s, NmpcSoftArgs q) {
+// REF: the T term on LAMBDA theta - rho (NmLtRho); cost0 and the theta entry of w_N alone change.
+template <bool SOFT, bool REF = false>
+__global__ void __launch_bounds__(64) nmpc_stage_rollout_kernel(NmpcArgs a, NmpcStageArgs s, NmpcSoftArgs q,
+                                                                NmpcRefArgs rf) {
     const int lane = threadIdx.x, b = blockIdx.x;
     if (b >= a.batch || a.done[b]) return;
     const int N = a.N, n = a.n, m = a.m, mx = a.mx, mu = a.mu, ms = mx + mu, mp = a.mp;
@@ -762,12 +841,13 @@ __global__ void __launch_bounds__(64) nmpc_stage_rollout_kernel(NmpcArgs a, Nmpc
         double wx[4];
         xgrad(NO_P, x, wx);
         double wt = thgrad(wx, 0.0);
+        const NmLtRho<REF> ltr(rf, b, cst);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             double w = 0.0;
 #pragma unroll
             for (int c2 = r; c2 < 4; ++c2) w += cst[NO_T + 4 * r + c2] * cst[NO_L + c2];
-            const double e = w * th;
+            const double e = ltr.row(w * th, r);
             J += e * e;
             wt += 2.0 * w * e;
         }
@@ -971,6 +1051,20 @@ __device__ __forceinline__ double nmd_tterm(const double* cst, double th, double
     }
     return g;
 }
+// the same on LAMBDA theta - rho (a set-point: NmLtRho<true>)
+__device__ __forceinline__ double nmd_tterm(const double* cst, double th, double& J, const NmLtRho<true>& ltr) {
+    double g = 0.0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        double w = 0.0;
+#pragma unroll
+        for (int c2 = r; c2 < 4; ++c2) w += cst[NO_T + 4 * r + c2] * cst[NO_L + c2];
+        const double e = ltr.row(w * th, r);
+        J += e * e;
+        g += 2.0 * w * e;
+    }
+    return g;
+}
 // value of row i of [F_x; F_u]: F_x (x - x_eq) - h_x (i < mx) or F_u v - h_u
 __device__ __forceinline__ double nmd_xrow(const double* cst, int mx, int i, const double (&x)[4]) {
     double cv = -cst[NO_HX + i];
@@ -1044,7 +1138,11 @@ __device__ __forceinline__ void nmd_load_iterate(const NmpcArgs& a, const NmpcDm
     }
 }
 
-__global__ void __launch_bounds__(64) nmpc_dms_linearize_kernel(NmpcArgs a, NmpcStageArgs s, NmpcDmsArgs m) {
+// REF: the lane that owns stage N forms Lt rho for its T term (NmLtRho); rf is read by that
+// instantiation alone
+template <bool REF>
+__global__ void __launch_bounds__(64) nmpc_dms_linearize_kernel(NmpcArgs a, NmpcStageArgs s, NmpcDmsArgs m,
+                                                                NmpcRefArgs rf) {
     const int lane = threadIdx.x, b = blockIdx.x;
     if (b >= a.batch || a.done[b]) return;
     const int N = a.N, mx = a.mx, mu = a.mu, ms = mx + mu, mp = a.mp;
@@ -1115,7 +1213,8 @@ __global__ void __launch_bounds__(64) nmpc_dms_linearize_kernel(NmpcArgs a, Nmpc
             // terminal P on x_N, T on LAMBDA theta
             nmd_xgrad(cst, NO_P, x, th, J, wx);
             wt = nmd_thgrad(cst, wx, 0.0);
-            wt += nmd_tterm(cst, th, J);
+            if constexpr (REF) wt += nmd_tterm(cst, th, J, NmLtRho<true>(rf, b, cst));
+            else wt += nmd_tterm(cst, th, J);
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) wg[nmpc_dms_w_index(k, i)] = wx[i];
@@ -1243,7 +1342,8 @@ __global__ void __launch_bounds__(64) nmpc_dms_backmap_kernel(NmpcArgs a, NmpcSt
 // one wave per (instance, trial): cost, row violation V and defect norm E = sum_k |f_k - x_{k+1}|_1
 // at (X, z) + 2^-t (dX, d), the stages in parallel; costT = J, violT = V + E (not finite where an f_k
 // is not: the update rejects the trial)
-__global__ void __launch_bounds__(64) nmpc_dms_trial_kernel(NmpcArgs a, NmpcDmsArgs m) {
+template <bool REF>
+__global__ void __launch_bounds__(64) nmpc_dms_trial_kernel(NmpcArgs a, NmpcDmsArgs m, NmpcRefArgs rf) {
     const int lane = threadIdx.x;
     const int nt = a.ntrial;
     const int b = blockIdx.x / nt, t = blockIdx.x % nt;
@@ -1276,7 +1376,8 @@ __global__ void __launch_bounds__(64) nmpc_dms_trial_kernel(NmpcArgs a, NmpcDmsA
             for (int i = mx; i < ms; ++i) V += fmax(nmd_urow(cst, mx, i, vk), 0.0);
         } else {
             nmd_xgrad(cst, NO_P, x, th, J, wx);
-            nmd_tterm(cst, th, J);
+            if constexpr (REF) nmd_tterm(cst, th, J, NmLtRho<true>(rf, b, cst));
+            else nmd_tterm(cst, th, J);
         }
         if (nmpc_dms_has_state_rows(N, k))
             for (int i = 0; i < mx; ++i) V += fmax(nmd_xrow(cst, mx, i, x), 0.0);
@@ -1423,6 +1524,9 @@ static const NmpcSoftArgs nm_hard = {};
 static bool nmpc_soft_args_ok(const NmpcSoftArgs* q) {
     return !q || ((q->xs_lin || q->xs_quad) && q->xsl && q->xsq && q->sx && q->pen0 && q->plin);
 }
+// the set-point of a launch: given with its array, or null
+static const NmpcRefArgs nm_noref = {};
+static bool nmpc_ref_args_ok(const NmpcRefArgs* r) { return !r || (r->xref && r->sref >= 0); }
 
 hipError_t launch_nmpc_stage_table(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
                                    const NmpcSoftArgs* q) {
@@ -1433,12 +1537,15 @@ hipError_t launch_nmpc_stage_table(const NmpcArgs& a, const NmpcStageArgs& s, hi
 }
 
 hipError_t launch_nmpc_stage_rollout(const NmpcArgs& a, const NmpcStageArgs& s, hipStream_t st,
-                                     const NmpcSoftArgs* q) {
+                                     const NmpcSoftArgs* q, const NmpcRefArgs* r) {
     if (!nmpc_stage_args_ok(a) || !s.A || !s.B || !s.w || !s.xlb || !s.xub || !s.ulb || !s.uub ||
-        (a.mp > 0 && !s.hp) || !s.map || !a.rhs || !a.cost0 || !nmpc_soft_args_ok(q))
+        (a.mp > 0 && !s.hp) || !s.map || !a.rhs || !a.cost0 || !nmpc_soft_args_ok(q) || !nmpc_ref_args_ok(r))
         return hipErrorInvalidValue;
-    if (q) hipLaunchKernelGGL(nmpc_stage_rollout_kernel<true>, dim3(a.batch), dim3(64), 0, st, a, s, *q);
-    else hipLaunchKernelGGL(nmpc_stage_rollout_kernel<false>, dim3(a.batch), dim3(64), 0, st, a, s, nm_hard);
+    const dim3 g(a.batch), w(64);
+    if (q && r) hipLaunchKernelGGL((nmpc_stage_rollout_kernel<true, true>), g, w, 0, st, a, s, *q, *r);
+    else if (r) hipLaunchKernelGGL((nmpc_stage_rollout_kernel<false, true>), g, w, 0, st, a, s, nm_hard, *r);
+    else if (q) hipLaunchKernelGGL((nmpc_stage_rollout_kernel<true>), g, w, 0, st, a, s, *q, nm_noref);
+    else hipLaunchKernelGGL((nmpc_stage_rollout_kernel<false>), g, w, 0, st, a, s, nm_hard, nm_noref);
     return hipGetLastError();
 }
 
@@ -1463,11 +1570,12 @@ hipError_t launch_nmpc_dms_start(const NmpcArgs& a, const NmpcDmsArgs& m, hipStr
 }
 
 hipError_t launch_nmpc_dms_linearize(const NmpcArgs& a, const NmpcStageArgs& s, const NmpcDmsArgs& m,
-                                     hipStream_t st) {
+                                     hipStream_t st, const NmpcRefArgs* r) {
     if (!nmpc_dms_args_ok(a, m) || !m.c || !s.A || !s.B || !s.w || !s.xlb || !s.xub || !s.ulb || !s.uub ||
-        (a.mp > 0 && !s.hp) || !s.map || !a.rhs || !a.cost0 || !a.done)
+        (a.mp > 0 && !s.hp) || !s.map || !a.rhs || !a.cost0 || !a.done || !nmpc_ref_args_ok(r))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nmpc_dms_linearize_kernel, dim3(a.batch), dim3(64), 0, st, a, s, m);
+    if (r) hipLaunchKernelGGL(nmpc_dms_linearize_kernel<true>, dim3(a.batch), dim3(64), 0, st, a, s, m, *r);
+    else hipLaunchKernelGGL(nmpc_dms_linearize_kernel<false>, dim3(a.batch), dim3(64), 0, st, a, s, m, nm_noref);
     return hipGetLastError();
 }
 
@@ -1481,10 +1589,12 @@ hipError_t launch_nmpc_dms_backmap(const NmpcArgs& a, const NmpcStageArgs& s, co
     return hipGetLastError();
 }
 
-hipError_t launch_nmpc_dms_trial(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st) {
-    if (!nmpc_dms_args_ok(a, m) || !m.dX || !a.d || !a.costT || !a.violT || a.ntrial < 1)
+hipError_t launch_nmpc_dms_trial(const NmpcArgs& a, const NmpcDmsArgs& m, hipStream_t st, const NmpcRefArgs* r) {
+    if (!nmpc_dms_args_ok(a, m) || !m.dX || !a.d || !a.costT || !a.violT || a.ntrial < 1 || !nmpc_ref_args_ok(r))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nmpc_dms_trial_kernel, dim3(a.batch * a.ntrial), dim3(64), 0, st, a, m);
+    const dim3 g(a.batch * a.ntrial), w(64);
+    if (r) hipLaunchKernelGGL(nmpc_dms_trial_kernel<true>, g, w, 0, st, a, m, *r);
+    else hipLaunchKernelGGL(nmpc_dms_trial_kernel<false>, g, w, 0, st, a, m, nm_noref);
     return hipGetLastError();
 }
 
@@ -1511,13 +1621,21 @@ bool nmpc_supported(int N, int mx, int mu) {
            mu >= 0 && mu <= NMPC_MAXMU;
 }
 
-hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st, const NmpcSoftArgs* q) {
+hipError_t launch_nmpc_rollout(const NmpcArgs& a, int gn, hipStream_t st, const NmpcSoftArgs* q,
+                               const NmpcRefArgs* r) {
     if (!nmpc_supported(a.N, a.mx, a.mu) || a.n != a.N + 1 || a.nr != 5 * a.N + 8 ||
-        a.m != a.N * (a.mx + a.mu) + a.mp || (q && (gn || !nmpc_soft_args_ok(q))))
+        a.m != a.N * (a.mx + a.mu) + a.mp || (q && (gn || !nmpc_soft_args_ok(q))) || !nmpc_ref_args_ok(r))
         return hipErrorInvalidValue;
-    if (gn) hipLaunchKernelGGL((nmpc_rollout_kernel<true>), dim3(a.batch), dim3(64), 0, st, a, nm_hard);
-    else if (q) hipLaunchKernelGGL((nmpc_rollout_kernel<false, true>), dim3(a.batch * a.ntrial), dim3(64), 0, st, a, *q);
-    else hipLaunchKernelGGL((nmpc_rollout_kernel<false>), dim3(a.batch * a.ntrial), dim3(64), 0, st, a, nm_hard);
+    const dim3 g1(a.batch), gt(a.batch * a.ntrial), w(64);
+    if (r) {
+        if (gn) hipLaunchKernelGGL((nmpc_rollout_kernel<true, false, true>), g1, w, 0, st, a, nm_hard, *r);
+        else if (q) hipLaunchKernelGGL((nmpc_rollout_kernel<false, true, true>), gt, w, 0, st, a, *q, *r);
+        else hipLaunchKernelGGL((nmpc_rollout_kernel<false, false, true>), gt, w, 0, st, a, nm_hard, *r);
+        return hipGetLastError();
+    }
+    if (gn) hipLaunchKernelGGL((nmpc_rollout_kernel<true>), g1, w, 0, st, a, nm_hard, nm_noref);
+    else if (q) hipLaunchKernelGGL((nmpc_rollout_kernel<false, true>), gt, w, 0, st, a, *q, nm_noref);
+    else hipLaunchKernelGGL((nmpc_rollout_kernel<false>), gt, w, 0, st, a, nm_hard, nm_noref);
     return hipGetLastError();
 }
 
@@ -1537,11 +1655,34 @@ hipError_t launch_nmpc_loop_shift(int batch, int N, int steps, int t, double* z,
     return hipGetLastError();
 }
 
-hipError_t launch_nmpc_loop_advance(const NmpcAdvanceArgs& a, hipStream_t st) {
+static const NmpcTrackArgs nm_notrack = {};
+// a schedule comes with the slot array it is copied into
+static bool nmpc_track_args_ok(const NmpcTrackArgs& k) {
+    return k.sref >= 0 && k.sdist >= 0 && (!k.ref) == (!k.xr);
+}
+
+hipError_t launch_nmpc_loop_advance(const NmpcAdvanceArgs& a, hipStream_t st, const NmpcTrackArgs* k) {
     // the shift stages N <= 128 doubles in LDS
-    if (a.batch < 1 || a.N < 1 || a.N > NMPC_MAXN || a.N > NM_WAVE * NM_CPL || a.steps < 1)
+    if (a.batch < 1 || a.N < 1 || a.N > NMPC_MAXN || a.N > NM_WAVE * NM_CPL || a.steps < 1 ||
+        (k && !nmpc_track_args_ok(*k)))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nmpc_loop_advance_kernel, dim3(a.batch), dim3(64), 0, st, a);
+    if (k) hipLaunchKernelGGL(nmpc_loop_advance_kernel<true>, dim3(a.batch), dim3(64), 0, st, a, *k);
+    else hipLaunchKernelGGL(nmpc_loop_advance_kernel<false>, dim3(a.batch), dim3(64), 0, st, a, nm_notrack);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_track_init(int batch, const NmpcTrackArgs& k, hipStream_t st) {
+    if (batch < 1 || !k.ref || !k.xr || k.sref < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_track_init_kernel, dim3((4 * batch + 255) / 256), dim3(256), 0, st, batch, k);
+    return hipGetLastError();
+}
+
+hipError_t launch_nmpc_track_plant(const NmpcAdvanceArgs& a, const NmpcTrackArgs& k, int t, hipStream_t st) {
+    // the step-synchronous loop points the solves at the schedule itself: no slot array
+    if (a.batch < 1 || a.N < 1 || a.N > NMPC_MAXN || t < 0 || t >= a.steps || k.sdist < 0 || !a.z || !a.s ||
+        !a.X || !a.U || !a.flag)
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(nmpc_track_plant_kernel, dim3((a.batch + 255) / 256), dim3(256), 0, st, a, k, t);
     return hipGetLastError();
 }
 

@@ -92,4 +92,48 @@ BQP_HD inline void nmpc_advance_next(const NmpcAdvanceArgs& a, int b, int t) {
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// set-point schedule and disturbed plant (bqp_closed_loop_nmpc_track): what the advance does in
+// addition for a due instance.  A separate, trailing kernel argument of the advance and of the
+// step-synchronous loop's plant launch, so that NmpcAdvanceArgs keeps its layout.
+// ------------------------------------------------------------------------------------------
+struct NmpcTrackArgs {
+    const double* ref;    // set-point schedule, absolute: steps x 4 per instance; may be null
+    int64_t sref;         // doubles between two instances' schedules; 0: one schedule for the batch
+    const double* dist;   // additive state disturbance: steps x 4 per instance; may be null (zero)
+    int64_t sdist;        // as sref
+    double* THETA;        // batch x steps, theta of every step's solution; may be null
+    double* xr;           // batch x 4: the set-point of the step each instance is at (the solves'
+                          // x_ref); null without a schedule
+};
+
+// entry i of step t of instance b in a schedule of stride `stride` (0: shared by the batch)
+BQP_HD inline int64_t nmpc_track_at(int64_t stride, int b, int t, int i) {
+    return (int64_t)b * stride + (int64_t)t * 4 + i;
+}
+
+// the next set-point is read only while steps remain: ref[b, steps] does not exist
+BQP_HD inline bool nmpc_track_has_next(int steps, int t) { return t + 1 < steps; }
+
+BQP_HD inline int64_t nmpc_track_theta_at(int steps, int b, int t) { return (int64_t)b * steps + t; }
+
+// theta of the step-t solution of instance b into the log (z: the instance's N + 1 variables,
+// before the shift, which keeps theta anyway)
+BQP_HD inline void nmpc_track_log(const NmpcTrackArgs& k, int steps, int N, int b, int t, const double* zb) {
+    if (k.THETA) k.THETA[nmpc_track_theta_at(steps, b, t)] = zb[N];
+}
+
+// the plant's state after step t, disturbed: one addition per entry, rounded once - the value the
+// log stores and the next solve measures
+BQP_HD inline void nmpc_track_disturb(const NmpcTrackArgs& k, int b, int t, double (&x)[4]) {
+    if (!k.dist) return;
+    for (int i = 0; i < 4; ++i) x[i] = x[i] + k.dist[nmpc_track_at(k.sdist, b, t, i)];
+}
+
+// the set-point of step t + 1 into the instance's current-reference slot, while steps remain
+BQP_HD inline void nmpc_track_next_ref(const NmpcTrackArgs& k, int steps, int b, int t) {
+    if (!k.ref || !k.xr || !nmpc_track_has_next(steps, t)) return;
+    for (int i = 0; i < 4; ++i) k.xr[(int64_t)b * 4 + i] = k.ref[nmpc_track_at(k.sref, b, t + 1, i)];
+}
+
 }  // namespace bqp
