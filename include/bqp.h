@@ -360,6 +360,20 @@ int bqp_lbmpc_linearize_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
  * delta/10) - models/trueModel.m:14/48 behind functions/transitionTrue.m, the plant of the
  * fmincon loops (functions/ocpLMPC.m:11-40, ocpLBMPC.m); with bqp.LMPC's problem this runs
  * examples/LMPC_RunExample.m's loop.
+ *
+ * Per-instance plant coefficients (plant_par; models/trueModel.m:32-41 names them wn, zeta, beta,
+ * x2_c): p = [x2_c, 1/beta^2, wn^2, 2 zeta wn] in
+ *   f0 = -x1 + p0 + 1 + 3 (x0/2) - x0^3/2        f2 = x3
+ *   f1 = (x0 + 1 - x2 sqrt(x1)) p1               f3 = -p2 x2 - p3 x3 + p2 u
+ * with the nominal plant p = [0, 1, 1000, 2 sqrt(500)].  Honoured, with both MG plants wherever the
+ * loop admits them, by every closed loop below: bqp_closed_loop_ocp, _lbmpc (the window's Y and XL
+ * then see the perturbed plant), _sqp, _track (MG plants; BQP_PLANT_LINEAR has Ap, Bp and returns
+ * BQP_E_ARG), _nmpc and _nmpc_track (every route, both loop modes; the model inside the solve
+ * stays nominal), host and _device forms.  plant_par = NULL launches exactly the kernels it
+ * launched before the member existed.  The host entries return BQP_E_ARG for a non-finite
+ * coefficient, p1 <= 0, p2 <= 0, p3 < 0, a stride that is neither 0 nor at least one instance's
+ * block, and a plant_par_sched other than 0 or 1; on the _device entries the values are the
+ * caller's duty, as for x_eq.  No MEX field.
  * ---------------------------------------------------------------------------------------- */
 #define BQP_PLANT_MG_RK4 1
 #define BQP_PLANT_MG_ODE23 2
@@ -370,6 +384,13 @@ typedef struct {
     double delta;        /* plant step (s) */
     const double* x_eq;  /* nx working point (device memory in the _device variant) */
     const double* u_eq;  /* nu */
+    /* trailing members: a zero-initialised structure is the loop as it was */
+    const double* plant_par;   /* NULL: the nominal plant, every kernel as before (device memory
+                                  in the _device variant) */
+    int64_t       splant_par;  /* doubles between two instances' parameters; 0 = shared by the batch */
+    int           plant_par_sched; /* 0: 4 doubles per instance, constant over the loop;
+                                      1: steps*4 per instance, row t is the plant that takes
+                                      X[b,t] to X[b,t+1]; row `steps` is never read */
 } bqp_closed_loop;
 
 int bqp_closed_loop_ocp(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* data,
@@ -469,6 +490,7 @@ int bqp_closed_loop_sqp_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
  *   x+ = x_eq + Ap (x - x_eq) + Bp (u - u_eq) + d_t     (d_t = dist[b, t, :])
  * for any (nx, nu, np) the structured solve accepts; cl->delta is not used.  Ap, Bp and dist
  * belong to that plant alone: with the MG plants (nx = 4, nu = 1) a non-NULL one is BQP_E_ARG.
+ * cl->plant_par belongs to the MG plants alone: with BQP_PLANT_LINEAR a non-NULL one is BQP_E_ARG.
  * Otherwise as bqp_closed_loop_ocp: data->x0 is ignored (and may be NULL), a step whose solve
  * ends != 1 still applies the solver's u_0, the loop's time goes to bqp_last_kernel_ms.
  * ---------------------------------------------------------------------------------------- */
@@ -719,7 +741,9 @@ int bqp_nmpc_dms_qp_device(bqp_handle h, const bqp_nmpc_dims* d, int batch, cons
  * (batch*steps, may be NULL) per solve.  The loop's time goes to bqp_last_kernel_ms (6 launches
  * per round; on the stage route 6 and the structured solve's repair launch where opt->polish
  * asks for one; with shooting = 1 one more, the warm start of the states), its rounds to bqp_last_loop_rounds.  The _device variant synchronises its stream
- * while it polls for the instances that have finished. */
+ * while it polls for the instances that have finished.  cl->plant_par steps a plant with other
+ * coefficients than the model's (every route, both loop modes, the same bits in both); the solve's
+ * model stays the nominal one. */
 int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
                          const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,
                          double* X, double* U, int* exitflag, int* iterations);
@@ -749,8 +773,10 @@ typedef struct {
  * also logs theta, adds the disturbance and, while steps remain, takes the instance's next
  * set-point (it never reads ref[b, steps]); both modes return the same bits.  tr = NULL is
  * bqp_closed_loop_nmpc.  steps = 0 returns X = x_init.  A non-finite entry of ref or dist is
- * BQP_E_ARG on the host entry point.  Not covered: a set-point that varies over the horizon, a
- * plant whose parameters differ from the model's (the disturbance is additive), a MEX field. */
+ * BQP_E_ARG on the host entry point.  A plant whose parameters differ from the model's is
+ * cl->plant_par (bqp_closed_loop), with or without a track: in the asynchronous loop instance b
+ * reads the row of its own step.  Not covered: a set-point that varies over the horizon, plant
+ * parameters inside the solve's model (it stays nominal), a MEX field. */
 int bqp_closed_loop_nmpc_track(bqp_handle h, const bqp_nmpc_dims* d, int batch, const bqp_nmpc_data* data,
                                const bqp_options* opt, const bqp_closed_loop* cl, const double* x_init,
                                const bqp_nmpc_track* tr, double* X, double* U, int* exitflag,

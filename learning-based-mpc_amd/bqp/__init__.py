@@ -9,7 +9,7 @@ from .ocp import OcpProblem, solve_ocp  # noqa: F401
 from .mpc import LMPC, TrackingLBMPC, TrackingLMPC, TrackingMPC  # noqa: F401
 from .quadprog import quadprog  # noqa: F401
 from .lbmpc import LBMPC, DMSLBMPC, HybridLBMPC, nw_oracle  # noqa: F401
-from .loop import closed_loop, closed_loop_sqp  # noqa: F401
+from .loop import closed_loop, closed_loop_sqp, mg_plant_params, mg_steady_state  # noqa: F401
 from .nmpc import NMPC, closed_loop_nmpc  # noqa: F401
 from . import condense, design, sets  # noqa: F401
 

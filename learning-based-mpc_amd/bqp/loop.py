@@ -22,8 +22,67 @@ _PLANTS = {'rk4': BQP_PLANT_MG_RK4, 'ode23': BQP_PLANT_MG_ODE23, 'linear': BQP_P
 
 
 class ClosedLoop(C.Structure):
+    # the trailing members (plant_params=) default to zero: the nominal plant
     _fields_ = [('plant', C.c_int), ('steps', C.c_int), ('delta', C.c_double),
-                ('x_eq', _lib._PD), ('u_eq', _lib._PD)]
+                ('x_eq', _lib._PD), ('u_eq', _lib._PD),
+                ('plant_par', _lib._PD), ('splant_par', C.c_int64), ('plant_par_sched', C.c_int)]
+
+
+def mg_plant_params(x2_c=0.0, beta=1.0, wn2=1000.0, damping=2.0 * np.sqrt(500.0), wn=None, zeta=None):
+    """The Moore-Greitzer plant's coefficient vector p = [x2_c, 1/beta^2, wn^2, 2 zeta wn]
+    (models/trueModel.m:32-41 names x2_c, beta, wn, zeta) as plant_params= takes it; the arguments
+    broadcast against each other, the result has their common shape + (4,).  wn2 and damping are
+    wn^2 and 2 zeta wn themselves; wn= replaces wn2 by wn^2, and zeta= (with wn, or with sqrt(wn2))
+    replaces damping by 2 zeta wn.  Without arguments: the nominal plant [0, 1, 1000, 2 sqrt(500)],
+    exactly."""
+    if wn is not None:
+        wn2 = np.square(np.asarray(wn, float))
+    if zeta is not None:
+        w = np.asarray(wn, float) if wn is not None else np.sqrt(np.asarray(wn2, float))
+        damping = 2.0 * np.asarray(zeta, float) * w
+    beta = np.asarray(beta, float)
+    parts = np.broadcast_arrays(np.asarray(x2_c, float), 1.0 / (beta * beta), np.asarray(wn2, float),
+                                np.asarray(damping, float))
+    return np.ascontiguousarray(np.stack(parts, axis=-1), dtype=np.float64)
+
+
+def mg_steady_state(params, x1):
+    """(x_s, u_s) of the plant with coefficients params (..., 4) at the mass flow x1:
+    x2 = x2_c + 1 + 1.5 x1 - x1^3 / 2, x3 = (x1 + 1) / sqrt(x2), x4 = 0, u = x3 - independent of
+    beta, wn and zeta.  x_s (..., 4), u_s (...,), broadcast over params[..., 0] and x1: the offset a
+    controller designed at the nominal working point leaves on a perturbed plant is read off it."""
+    p = np.asarray(params, float)
+    x2c, x1 = np.broadcast_arrays(p[..., 0], np.asarray(x1, float))
+    x2 = x2c + 1.0 + 1.5 * x1 - x1 * x1 * x1 / 2.0
+    x3 = (x1 + 1.0) / np.sqrt(x2)
+    return np.stack([x1, x2, x3, np.zeros_like(x3)], axis=-1), x3
+
+
+def _plant_params(a, b, steps):
+    """plant_params= as bqp_closed_loop takes it: (array, stride, sched) from (4,) - one plant for
+    the batch -, (batch, 4), (steps, 4) - a schedule shared by the batch - or (batch, steps, 4).
+    With batch == steps a (steps, 4) array is the shared schedule (the schedule shape is tried
+    first, as nmpc._schedule tries its own)."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.shape == (4,):
+        return a, 0, 0
+    if a.shape == (steps, 4):
+        return a, 0, 1
+    if a.shape == (b, 4):
+        return a, 4, 0
+    if a.shape == (b, steps, 4):
+        return a, steps * 4, 1
+    raise ValueError('plant_params has the shape (4,), (batch, 4), (steps, 4) or (batch, steps, 4) with '
+                     '(batch, steps) = (%d, %d), not %r' % (b, steps, a.shape))
+
+
+def _set_plant_params(cl, plant_params, b, steps):
+    """fills the trailing members of cl; returns the arrays to keep alive (and to move, device=)"""
+    if plant_params is None:
+        return []
+    a, cl.splant_par, cl.plant_par_sched = _plant_params(plant_params, b, steps)
+    cl.plant_par = _lib.ptr(a)
+    return [a]
 
 
 class Learning(C.Structure):
@@ -80,7 +139,8 @@ class _Dev:
 
 
 def closed_loop(mpc, x_init, steps, delta=0.01, handle=None, learning=None, plant='rk4',
-                x_eq=None, u_eq=None, device=None, refs=None, dist=None, plant_model=None, **opts):
+                x_eq=None, u_eq=None, device=None, refs=None, dist=None, plant_model=None,
+                plant_params=None, **opts):
     """mpc: a TrackingLMPC / TrackingLBMPC (deviation coordinates around mpc.x_eq, mpc.u_eq), or
     an LMPC with the working point passed as x_eq / u_eq (functions/ocpLMPC.m: x_wp, u_wp);
     x_init (batch, n) absolute initial states.  Returns X (batch, steps+1, n), U (batch, steps,
@@ -108,7 +168,14 @@ def closed_loop(mpc, x_init, steps, delta=0.01, handle=None, learning=None, plan
     set-point in deviation from x_eq);
     plant='linear': x+ = x_eq + Ap (x - x_eq) + Bp (u - u_eq) + d_t (getTransitions.m) with
     plant_model=(Ap, Bp), each shared or per instance (default: the MPC's own A, B), and
-    dist (steps, n) or (batch, steps, n), the additive disturbance d_t (default: none)."""
+    dist (steps, n) or (batch, steps, n), the additive disturbance d_t (default: none).
+
+    plant_params (MG plants, every loop above, device= included): the plant's coefficients
+    p = [x2_c, 1/beta^2, wn^2, 2 zeta wn] (mg_plant_params builds them), (4,) for the batch,
+    (batch, 4) per instance, or a schedule (steps, 4) / (batch, steps, 4) whose row t is the plant
+    that takes X[:, t] to X[:, t + 1].  With batch == steps a (steps, 4) array is the schedule
+    shared by the batch.  The controller's model stays as it is; with learning= the window's Y and
+    XL see the perturbed plant.  Default: the nominal plant, the launches as they were."""
     lib = _lib.load()
     h = handle or _default_handle()
     x_init = np.ascontiguousarray(np.atleast_2d(x_init), dtype=np.float64)
@@ -120,13 +187,14 @@ def closed_loop(mpc, x_init, steps, delta=0.01, handle=None, learning=None, plan
             raise ValueError('closed_loop: learning= does not combine with refs / dist / '
                              'plant_model / plant=\'linear\'')
         return _closed_loop_track(lib, h, mpc, x_init, b, int(steps), delta, plant, x_eq, u_eq,
-                                  device, refs, dist, plant_model, opts)
+                                  device, refs, dist, plant_model, plant_params, opts)
     xeq = np.ascontiguousarray(mpc.x_eq if x_eq is None else np.ravel(x_eq), dtype=np.float64)
     ueq = np.ascontiguousarray(mpc.u_eq if u_eq is None else np.ravel(u_eq), dtype=np.float64)
     dims, data, batch, keep = pack(prob, x_init - xeq)
     cl = ClosedLoop(_PLANTS[plant], int(steps), float(delta), _lib.ptr(xeq), _lib.ptr(ueq))
+    par = _set_plant_params(cl, plant_params, b, int(steps))
     if device is not None:
-        return _closed_loop_device(lib, h, mpc, dims, data, keep, cl, [xeq, ueq], x_init, b, steps,
+        return _closed_loop_device(lib, h, mpc, dims, data, keep, cl, [xeq, ueq] + par, x_init, b, steps,
                                    learning, device, opts)
     X = np.zeros((b, steps + 1, prob.nx)); U = np.zeros((b, steps, prob.nu))
     flags = np.zeros((b, steps), np.int32)
@@ -190,7 +258,7 @@ def _shared_or_batch(a, b, shape, name):
 
 
 def _closed_loop_track(lib, h, mpc, x_init, b, steps, delta, plant, x_eq, u_eq, device, refs, dist,
-                       plant_model, opts):
+                       plant_model, plant_params, opts):
     """bqp_closed_loop_track(_device): the closed loop with a reference schedule and / or the
     linear plant (see closed_loop)"""
     prob = mpc.prob
@@ -203,6 +271,7 @@ def _closed_loop_track(lib, h, mpc, x_init, b, steps, delta, plant, x_eq, u_eq, 
         raise ValueError("closed_loop: dist= and plant_model= belong to plant='linear'")
     dims, data, _, keep = pack(prob, x_init - xeq)
     cl = ClosedLoop(_PLANTS[plant], steps, float(delta), _lib.ptr(xeq), _lib.ptr(ueq))
+    par = _set_plant_params(cl, plant_params, b, steps)
     tr = _lib.Track()
     arrays = []
     if plant_model is not None:
@@ -234,7 +303,7 @@ def _closed_loop_track(lib, h, mpc, x_init, b, steps, delta, plant, x_eq, u_eq, 
     else:
         d = _Dev(device)
         d.inputs(data, keep)
-        d.inputs(cl, [xeq, ueq])
+        d.inputs(cl, [xeq, ueq] + par)
         d.inputs(tr, arrays)
         xi = d.array(x_init)
         X = d.out((b, steps + 1, nx)); U = d.out((b, steps, nu))
@@ -258,7 +327,7 @@ def _closed_loop_track(lib, h, mpc, x_init, b, steps, delta, plant, x_eq, u_eq, 
 
 def closed_loop_sqp(mpc, x_init, steps, learning=None, warm=True, delta=0.01, handle=None,
                     max_iter=200, tol=1e-8, log_z=False, plant='rk4', x_eq=None,
-                    u_eq=None, polish=0, device=None):
+                    u_eq=None, polish=0, device=None, plant_params=None):
     """Learned-model NLP closed loop on the GPU (bqp_closed_loop_sqp): per step the batched
     Gauss-Newton SQP of mpc (a DMSLBMPC - DMS_LBMPC_casadi.m:163-218 -, HybridLBMPC -
     hybrid_LBMPC_casadi.m:163-204 - or LBMPC) at the measured states, one RK4 plant step with the
@@ -276,7 +345,10 @@ def closed_loop_sqp(mpc, x_init, steps, learning=None, warm=True, delta=0.01, ha
     steps), XL (batch, steps+1, n) the learned one-step predictions, window (batch, q, 8) the
     final windows in ring order, and with log_z every step's solution Z (batch, steps, nz).
     device (a GPU index or torch device): bqp_closed_loop_sqp_device on device memory and torch's
-    current stream there; every result is a torch tensor on that device."""
+    current stream there; every result is a torch tensor on that device.
+    plant_params: the plant's coefficients, as closed_loop takes them ((4,), (batch, 4), (steps, 4)
+    or (batch, steps, 4); with batch == steps a (steps, 4) array is the shared schedule): each
+    instance's window then learns its own plant's mismatch."""
     lib = _lib.load()
     h = handle or _default_handle()
     learning = dict(learning or {})
@@ -302,13 +374,14 @@ def closed_loop_sqp(mpc, x_init, steps, learning=None, warm=True, delta=0.01, ha
     if device is not None:
         return _closed_loop_sqp_device(lib, h, mpc, dims, dd, keep, bin0, Bx, x_eq, u_eq, x_init, b,
                                        steps, q, mask, learning, warm, delta, plant, max_iter, tol,
-                                       log_z, polish, device)
+                                       log_z, polish, device, plant_params)
     X = np.zeros((b, steps + 1, mpc.n)); U = np.zeros((b, steps, mpc.m))
     XL = np.zeros_like(X); win = np.zeros((b, q, 8))
     flags = np.zeros((b, steps), np.int32); its = np.zeros((b, steps), np.int32)
     Z = np.zeros((b, steps, mpc.nz)) if log_z else None
     sl = _lib.SqpLoop(_lib.ptr(bin0), _lib.ptr(Bx), int(bool(warm)), _lib.ptr(Z), _lib.iptr(its))
     cl = ClosedLoop(_PLANTS[plant], int(steps), float(delta), _lib.ptr(x_eq), _lib.ptr(u_eq))
+    par = _set_plant_params(cl, plant_params, b, int(steps))
     lw = Learning(q, mask, float(learning.get('bandwidth', 0.0)), float(learning.get('lambda_', 0.0)),
                   _lib.ptr(XL), _lib.ptr(win))
     o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
@@ -324,7 +397,7 @@ def closed_loop_sqp(mpc, x_init, steps, learning=None, warm=True, delta=0.01, ha
 
 def _closed_loop_sqp_device(lib, h, mpc, dims, dd, keep, bin0, Bx, x_eq, u_eq, x_init, b, steps, q,
                             mask, learning, warm, delta, plant, max_iter, tol, log_z, polish,
-                            device):
+                            device, plant_params=None):
     d = _Dev(device)
     d.inputs(dd, keep + [mpc.Ain_cm])
     X = d.out((b, steps + 1, mpc.n)); U = d.out((b, steps, mpc.m))
@@ -333,6 +406,8 @@ def _closed_loop_sqp_device(lib, h, mpc, dims, dd, keep, bin0, Bx, x_eq, u_eq, x
     Z = d.out((b, steps, mpc.nz)) if log_z else None
     sl = _lib.SqpLoop(d.p(d.array(bin0)), d.p(d.array(Bx)), int(bool(warm)), d.p(Z), d.p(its))
     cl = ClosedLoop(_PLANTS[plant], int(steps), float(delta), d.p(d.array(x_eq)), d.p(d.array(u_eq)))
+    for a in _set_plant_params(cl, plant_params, b, int(steps)):
+        cl.plant_par = d.p(d.array(a))
     lw = Learning(q, mask, float(learning.get('bandwidth', 0.0)), float(learning.get('lambda_', 0.0)),
                   d.p(XL), d.p(win))
     o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)

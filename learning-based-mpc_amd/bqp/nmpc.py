@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from .lbmpc import _upper_factor
-from .loop import ClosedLoop
+from .loop import ClosedLoop, _set_plant_params
 from .ocp import OcpResult, _default_handle
 
 _BQP_PLANT_MG_RK4 = 1
@@ -310,7 +310,7 @@ def _schedule(a, b, steps, name):
 
 def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, polish=0,
                      subproblem='dense', xs_lin=None, xs_quad=None, shooting='single', refs=None,
-                     dist=None, x_ref=None):
+                     dist=None, x_ref=None, plant_params=None):
     """Closed loop of DMS_tracking_NMPC_casadi.m:153-207 for a batch of initial states x_init
     (batch, 4), absolute: per step the solve at the measured state, the RK4 plant with u_0, and
     the warm start (z shifted one stage, last move repeated, theta kept).  Every instance advances
@@ -323,7 +323,12 @@ def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, p
     the cost); dist, same shapes: X[t + 1] = dynamic(delta, X[t], U[t]) + dist[t].  With either, the
     loop is bqp_closed_loop_nmpc_track and the result also holds theta (batch, steps), the theta of
     every step's solution; with neither it is bqp_closed_loop_nmpc, as before.  x_ref: a constant
-    set-point, (4,) or (batch, 4), for the steps no schedule covers."""
+    set-point, (4,) or (batch, 4), for the steps no schedule covers.
+    plant_params: the coefficients p = [x2_c, 1/beta^2, wn^2, 2 zeta wn] of the plant the loop steps
+    (bqp.mg_plant_params), (4,), (batch, 4), or a schedule (steps, 4) / (batch, steps, 4) whose row t
+    takes X[:, t] to X[:, t + 1]; with batch == steps a (steps, 4) array is the schedule shared by the
+    batch, as for refs.  The model inside the solve stays nominal: the mismatch is the experiment.
+    Default: the nominal plant, the launches as they were."""
     lib = _lib.load()
     h = handle or _default_handle()
     xi = _f64(np.atleast_2d(x_init))
@@ -334,6 +339,7 @@ def closed_loop_nmpc(prob, x_init, steps, handle=None, max_iter=100, tol=1e-8, p
     xr = prob._ref(x_ref, b)
     dims, dd = prob._dims(subproblem, shooting), prob._data(soft=soft, x_ref=xr)
     cl = ClosedLoop(_BQP_PLANT_MG_RK4, steps, prob.delta, _lib.ptr(prob.x_eq), _lib.ptr(prob.u_eq))
+    par = _set_plant_params(cl, plant_params, b, steps)   # kept alive over the call
     o = _lib.options(max_iter=max_iter, tol_stat=tol, polish=polish)
     r = OcpResult(X=X, U=U, exitflag=fl, iterations=it)
     if refs is None and dist is None:

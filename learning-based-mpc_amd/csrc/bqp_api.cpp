@@ -1083,12 +1083,47 @@ int bqp_lbmpc_linearize(bqp_handle h, const bqp_lbmpc_dims* d, int batch, const 
 // ------------------------------------------------------------------------------------------
 // the loop description of the closed-loop entry points (cl non-null): plant, steps, sampling time
 // and working point; the plants are the Moore-Greitzer model's
+// bqp_closed_loop.plant_par (per-instance Moore-Greitzer coefficients, bqp_plant_par.h).  Every
+// entry: none with the linear plant, the schedule flag 0 or 1, a stride of 0 or at least one
+// instance's block.  A null plant_par leaves the other two members unread.
+static int plant_par_check(const bqp_closed_loop* cl) {
+    if (!cl->plant_par) return BQP_OK;
+    if (cl->plant == BQP_PLANT_LINEAR) return BQP_E_ARG;
+    if (cl->plant_par_sched != 0 && cl->plant_par_sched != 1) return BQP_E_ARG;
+    return bqp::plant_par_stride_ok(cl->splant_par, cl->steps, cl->plant_par_sched) ? BQP_OK : BQP_E_ARG;
+}
+
+// host entries, after plant_par_check: every row finite with 1/beta^2 > 0, wn^2 > 0, 2 zeta wn >= 0
+// (the device entries leave the values to the caller)
+static int plant_par_host_check(const bqp_closed_loop* cl, int batch) {
+    if (!cl->plant_par) return BQP_OK;
+    const int rows = cl->plant_par_sched ? cl->steps : 1;
+    for (int b = 0; b < (cl->splant_par == 0 ? 1 : batch); ++b)
+        for (int t = 0; t < rows; ++t)
+            if (!bqp::plant_par_row_ok(cl->plant_par + bqp::plant_par_at(cl->splant_par, cl->plant_par_sched, b, t)))
+                return BQP_E_ARG;
+    return BQP_OK;
+}
+
+// the host entries' copy of the coefficients to the device, into the loop description's copy
+static void stage_plant_par(Stage& st, const bqp_closed_loop* cl, int batch, bqp_closed_loop* cd) {
+    st.in(&cd->plant_par, cl->plant_par,
+          cl->plant_par ? (size_t)bqp::plant_par_span(batch, cl->splant_par, cl->steps, cl->plant_par_sched) : 0);
+}
+
+// what the plant and advance launchers take: null for the nominal plant (the kernels as they were)
+struct LoopPlantPar {
+    bqp::PlantPar pp;
+    explicit LoopPlantPar(const bqp_closed_loop* cl) : pp{cl->plant_par, cl->splant_par, cl->plant_par_sched} {}
+    const bqp::PlantPar* get() const { return pp.p ? &pp : nullptr; }
+};
+
 static int loop_check(const bqp_closed_loop* cl, int nx, int nu) {
     if ((cl->plant != BQP_PLANT_MG_RK4 && cl->plant != BQP_PLANT_MG_ODE23) || cl->steps <= 0 ||
         !(cl->delta > 0) || !cl->x_eq || !cl->u_eq)
         return BQP_E_ARG;
     if (nx != 4 || nu != 1) return BQP_E_UNSUPPORTED;
-    return BQP_OK;
+    return plant_par_check(cl);
 }
 
 static int closed_loop_impl(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_ocp_data* D,
@@ -1123,12 +1158,13 @@ static int closed_loop_impl(bqp_handle h, const bqp_ocp_dims* d, int batch, cons
     HIP_TRY(hipEventCreate(&e0.e));
     HIP_TRY(hipEventRecord(e0.e, st));
     int launches = 0;
+    const LoopPlantPar par(cl);
     for (int t = 0; t < cl->steps; ++t) {
         BQP_TRY(bqp_solve_ocp_batched_device(h, d, batch, &Dm, opt, xo, uo, th, nullptr, fl, nullptr,
                                              nullptr, stream));
         launches += h->launches + (lw ? 2 : 1);
         HIP_TRY(bqp::launch_mg_plant(cl->plant, batch, N, cl->steps, t, cl->delta, uo, fl, cl->x_eq, cl->u_eq,
-                                     s, X, U, exitflag, st));
+                                     s, X, U, exitflag, st, par.get()));
         if (lw)
             HIP_TRY(bqp::launch_lbmpc_window(batch, cl->steps, t, lw->q, bw, lam, D->A, D->sA, D->B,
                                              D->sB, cl->x_eq, cl->u_eq, X, U, win, lw->XL, st));
@@ -1170,6 +1206,7 @@ static int closed_loop_host(bqp_handle h, const bqp_ocp_dims* d, int batch, cons
     BQP_TRY(ocp_soft_host_check(d, batch, D));
     // validate the loop description before sizing the staging buffers from it
     BQP_TRY(loop_check(cl, d->nx, d->nu));
+    BQP_TRY(plant_par_host_check(cl, batch));
     DevScope ds(h->device);
     const size_t B = batch, S = cl->steps, nx = d->nx, nu = d->nu;
     const size_t nX = B * (S + 1) * nx;
@@ -1183,6 +1220,7 @@ static int closed_loop_host(bqp_handle h, const bqp_ocp_dims* d, int batch, cons
     stage_ocp_data(st, d, batch, D, x_init, B * nx, &Dd);
     st.in(&cd.x_eq, cl->x_eq, nx);
     st.in(&cd.u_eq, cl->u_eq, nu);
+    stage_plant_par(st, cl, batch, &cd);
     st.out(&Xd, nX, X);
     st.out(&Ud, B * S * nu, U);
     if (lw) {
@@ -1233,6 +1271,7 @@ static int track_check(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp
     } else {
         return BQP_E_ARG;
     }
+    BQP_TRY(plant_par_check(cl));
     if (tr->nr < 0 || tr->sref < 0) return BQP_E_ARG;
     if (tr->nr > 0 && (!tr->Wr || !tr->ref)) return BQP_E_ARG;
     if (D->w && D->sw < 0) return BQP_E_ARG;
@@ -1281,11 +1320,12 @@ static int track_impl(bqp_handle h, const bqp_ocp_dims* d, int batch, const bqp_
     HIP_TRY(hipEventCreate(&e0.e));
     HIP_TRY(hipEventRecord(e0.e, st));
     int launches = 0;
+    const LoopPlantPar par(cl);
     for (int t = 0; t < cl->steps; ++t) {
         BQP_TRY(bqp_solve_ocp_batched_device(h, d, batch, &Dm, opt, xo, uo, th, nullptr, fl, nullptr,
                                              nullptr, stream));
         launches += h->launches + 1;
-        HIP_TRY(bqp::launch_track_advance(a, t, st));
+        HIP_TRY(bqp::launch_track_advance(a, t, st, par.get()));
     }
     // timing of the whole loop (solves + advance launches) on this stream
     HIP_TRY(hipEventRecord(h->ev1, st));
@@ -1310,6 +1350,7 @@ int bqp_closed_loop_track(bqp_handle h, const bqp_ocp_dims* d, int batch, const 
     // validate the whole description before sizing the staging buffers from it
     BQP_TRY(track_check(h, d, batch, D, cl, tr, x_init, X, U));
     BQP_TRY(ocp_soft_host_check(d, batch, D));
+    BQP_TRY(plant_par_host_check(cl, batch));
     DevScope ds(h->device);
     const size_t B = batch, S = cl->steps, nx = d->nx, nu = d->nu, np = d->np;
     const size_t nw = (size_t)(d->N + 1) * (nx + nu + np), nr = tr->nr;
@@ -1324,6 +1365,7 @@ int bqp_closed_loop_track(bqp_handle h, const bqp_ocp_dims* d, int batch, const 
     stage_ocp_data(st, d, batch, D, x_init, B * nx, &Dd);
     st.in(&cd.x_eq, cl->x_eq, nx);
     st.in(&cd.u_eq, cl->u_eq, nu);
+    stage_plant_par(st, cl, batch, &cd);
     st.in(&td.Ap, linear ? tr->Ap : nullptr, span(batch, tr->sAp, nx * nx));
     st.in(&td.Bp, linear ? tr->Bp : nullptr, span(batch, tr->sBp, nx * nu));
     st.in(&td.dist, linear ? tr->dist : nullptr, span(batch, tr->sdist, S * nx));
@@ -1404,6 +1446,7 @@ int bqp_closed_loop_sqp_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
     HIP_TRY(hipEventCreate(&e0.e));
     HIP_TRY(hipEventRecord(e0.e, st));
     int launches = 0;
+    const LoopPlantPar par(cl);
     // BQP_LB_SYNC selects the step-synchronous loop below (the asynchronous loop's bitwise
     // reference in tests/test_gpu_lbmpc_dms.py); BQP_LB_TRACE only adds diagnostics to either
     const bool sync_loop = getenv("BQP_LB_SYNC") != nullptr;
@@ -1440,7 +1483,7 @@ int bqp_closed_loop_sqp_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
         const int max_rounds = cl->steps * opt->max_iter;
         for (int r = 0; r < max_rounds; ++r) {
             BQP_TRY(sqp_iteration(a, qd, st));
-            HIP_TRY(bqp::launch_sqp_loop_advance(v, st));
+            HIP_TRY(bqp::launch_sqp_loop_advance(v, st, par.get()));
             launches += sqp_iteration_launches(a) + 1;
             int nf = 0;
             HIP_TRY(hipMemcpyAsync(&nf, nfin, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -1458,7 +1501,7 @@ int bqp_closed_loop_sqp_device(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
         HIP_TRY(bqp::launch_sqp_loop_u0(batch, nx, n, D->K, s, z, uo, it, cl->steps, t,
                                         sl->Z, sl->iterations, st));
         HIP_TRY(bqp::launch_mg_plant(cl->plant, batch, 1, cl->steps, t, cl->delta, uo, fl, cl->x_eq, cl->u_eq,
-                                     s, X, U, exitflag, st));
+                                     s, X, U, exitflag, st, par.get()));
         HIP_TRY(bqp::launch_lbmpc_window(batch, cl->steps, t, q, bw, lam, D->A, 0, D->B, 0,
                                          cl->x_eq, cl->u_eq, X, U, win, lw->XL, st));
         launches += 3;
@@ -1477,6 +1520,7 @@ int bqp_closed_loop_sqp(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
                         double* X, double* U, int* exitflag) {
     if (!h) return BQP_E_ARG;
     BQP_TRY(sqp_loop_check(d, batch, D, sl, cl, lw, x_init, X, U));
+    BQP_TRY(plant_par_host_check(cl, batch));
     DevScope ds(h->device);
     const size_t B = batch, S = cl->steps, nx = d->nx, nu = d->nu, m = d->m, q = d->q;
     const size_t n = (size_t)d->N * nu + d->np;
@@ -1496,6 +1540,7 @@ int bqp_closed_loop_sqp(bqp_handle h, const bqp_lbmpc_dims* d, int batch,
     st.in(&xi, x_init, B * nx);
     st.in(&cd.x_eq, cl->x_eq, nx);
     st.in(&cd.u_eq, cl->u_eq, nu);
+    stage_plant_par(st, cl, batch, &cd);
     st.out(&Xd, nX, X);
     st.out(&Ud, B * S * nu, U);
     st.out(&ld.XL, nX, lw->XL);
@@ -2317,6 +2362,7 @@ static int nmpc_loop_check(const bqp_nmpc_dims* d, int batch, const bqp_nmpc_dat
     if (cl->plant != BQP_PLANT_MG_RK4 || cl->steps < 0 || !(cl->delta > 0) || !cl->x_eq || !cl->u_eq ||
         (cl->steps > 0 && !U))
         return BQP_E_ARG;
+    BQP_TRY(plant_par_check(cl));
     return nmpc_soft_check(d, D);
 }
 
@@ -2376,6 +2422,7 @@ static int nmpc_loop_device(bqp_handle h, const bqp_nmpc_dims* d, int batch, con
     HIP_TRY(hipEventCreate(&e0.e));
     HIP_TRY(hipEventRecord(e0.e, st));
     int launches = 0, rounds = 0;
+    const LoopPlantPar par(cl);
     // the arguments of the advance (asynchronous) and of the track's plant launch (step-synchronous)
     bqp::NmpcAdvanceArgs v;
     memset(&v, 0, sizeof(v));
@@ -2449,7 +2496,7 @@ static int nmpc_loop_device(bqp_handle h, const bqp_nmpc_dims* d, int batch, con
                 HIP_TRY(bqp::launch_nmpc_dms_loop_states(batch, N, S, D->delta, D->u_eq, z, Xit, a.done, ts, st));
                 launches += 1;
             }
-            HIP_TRY(bqp::launch_nmpc_loop_advance(v, st, track ? &k : nullptr));
+            HIP_TRY(bqp::launch_nmpc_loop_advance(v, st, track ? &k : nullptr, par.get()));
             launches += 1;
             ++rounds;
             int nf = 0;
@@ -2476,9 +2523,9 @@ static int nmpc_loop_device(bqp_handle h, const bqp_nmpc_dims* d, int batch, con
         rounds += h->nmpc_rounds;
         // the plant reads u_0 - u_eq = z[b, 0] (stride n); a track's plant launch also adds the
         // disturbance and logs theta
-        if (track) HIP_TRY(bqp::launch_nmpc_track_plant(v, k, t, st));
+        if (track) HIP_TRY(bqp::launch_nmpc_track_plant(v, k, t, st, par.get()));
         else HIP_TRY(bqp::launch_mg_plant(cl->plant, batch, n, S, t, cl->delta, z, fl, cl->x_eq, cl->u_eq,
-                                          s, X, U, exitflag, st));
+                                          s, X, U, exitflag, st, par.get()));
         if (dms) {
             HIP_TRY(bqp::launch_nmpc_dms_loop_states(batch, N, S, D->delta, D->u_eq, z, Xit, nullptr, nullptr, st));
             launches += 1;
@@ -2518,6 +2565,7 @@ int bqp_closed_loop_nmpc_track(bqp_handle h, const bqp_nmpc_dims* d, int batch, 
     BQP_TRY(nmpc_loop_check(d, batch, D, cl, x_init, X, U));
     BQP_TRY(nmpc_track_check(tr, cl->steps));
     BQP_TRY(nmpc_host_check(d, batch, D));
+    BQP_TRY(plant_par_host_check(cl, batch));
     const size_t B = batch, S = cl->steps;
     if (tr && (!nmpc_all_finite(tr->ref, batch, tr->sref, S * 4) ||
                !nmpc_all_finite(tr->dist, batch, tr->sdist, S * 4)))
@@ -2535,6 +2583,7 @@ int bqp_closed_loop_nmpc_track(bqp_handle h, const bqp_nmpc_dims* d, int batch, 
     st.in(&xi, x_init, B * 4);
     st.in(&cd.x_eq, cl->x_eq, 4);
     st.in(&cd.u_eq, cl->u_eq, 1);
+    stage_plant_par(st, cl, batch, &cd);
     if (tr) {
         td.sref = tr->sref; td.sdist = tr->sdist;
         st.in(&td.ref, tr->ref, span(batch, tr->sref, S * 4));
@@ -2558,6 +2607,7 @@ int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const 
     if (!h) return BQP_E_ARG;
     BQP_TRY(nmpc_loop_check(d, batch, D, cl, x_init, X, U));
     BQP_TRY(nmpc_host_check(d, batch, D));
+    BQP_TRY(plant_par_host_check(cl, batch));
     DevScope ds(h->device);
     const size_t B = batch, S = cl->steps;
     Stage st(h);
@@ -2570,6 +2620,7 @@ int bqp_closed_loop_nmpc(bqp_handle h, const bqp_nmpc_dims* d, int batch, const 
     st.in(&xi, x_init, B * 4);
     st.in(&cd.x_eq, cl->x_eq, 4);
     st.in(&cd.u_eq, cl->u_eq, 1);
+    stage_plant_par(st, cl, batch, &cd);
     st.out(&Xd, B * (S + 1) * 4, X);
     st.out(&Ud, B * S, U);
     st.out(&Fd, B * S, exitflag);

@@ -7,6 +7,7 @@
 #include "bqp_nmpc_advance.h"
 #include "bqp_nmpc_dms.h"
 #include "bqp_nmpc_stage.h"
+#include "bqp_plant_par.h"
 #include "bqp_track.h"
 
 namespace bqp {
@@ -280,12 +281,15 @@ hipError_t launch_nmpc_loop_shift(int batch, int N, int steps, int t, double* z,
 // whose SQP has stopped logs its step, steps the plant and sets up its next solve
 // k (bqp_closed_loop_nmpc_track): also theta into its log, the disturbance onto the plant's state
 // and the next step's set-point; null: the advance as it was
-hipError_t launch_nmpc_loop_advance(const NmpcAdvanceArgs& a, hipStream_t st, const NmpcTrackArgs* k = nullptr);
+// pp (bqp_closed_loop.plant_par): the plant of each instance's own step; null: the nominal plant
+hipError_t launch_nmpc_loop_advance(const NmpcAdvanceArgs& a, hipStream_t st, const NmpcTrackArgs* k = nullptr,
+                                    const PlantPar* pp = nullptr);
 // bqp_closed_loop_nmpc_track, once per loop: the set-points of step 0 into k.xr
 hipError_t launch_nmpc_track_init(int batch, const NmpcTrackArgs& k, hipStream_t st);
 // bqp_closed_loop_nmpc_track, step-synchronous loop: mg_plant_kernel's step t of every instance from
 // z[b, 0] with the disturbance added and theta logged (the advance's arithmetic, lane for lane)
-hipError_t launch_nmpc_track_plant(const NmpcAdvanceArgs& a, const NmpcTrackArgs& k, int t, hipStream_t st);
+hipError_t launch_nmpc_track_plant(const NmpcAdvanceArgs& a, const NmpcTrackArgs& k, int t, hipStream_t st,
+                                   const PlantPar* pp = nullptr);
 
 // closed-loop simulation (bqp_plant.hip): Moore-Greitzer plant (RK4 step or MATLAB ode23,
 // BQP_PLANT_*) between batched solves
@@ -293,11 +297,13 @@ hipError_t launch_closed_loop_init(int batch, int nx, int steps, const double* x
                                    const double* xeq, double* s, double* X, hipStream_t st);
 hipError_t launch_mg_plant(int plant, int batch, int N, int steps, int t, double delta,
                            const double* uo, const int* fl, const double* xeq, const double* ueq,
-                           double* s, double* X, double* U, int* flags, hipStream_t st);
+                           double* s, double* X, double* U, int* flags, hipStream_t st,
+                           const PlantPar* pp = nullptr);
 // closed loop with a reference schedule (bqp_closed_loop_track; TrackArgs: bqp_track.h): after
 // the step-t solve, record it, step the plant and form the linear terms of step t + 1; t = -1
 // forms those of step 0 alone
-hipError_t launch_track_advance(const TrackArgs& a, int t, hipStream_t st);
+// pp (bqp_closed_loop.plant_par, MG plants only): per-instance plant coefficients; null: nominal
+hipError_t launch_track_advance(const TrackArgs& a, int t, hipStream_t st, const PlantPar* pp = nullptr);
 // learned-model NLP closed loop glue (bqp_closed_loop_sqp): per instance bin = bin0 + Bx s and
 // the warm start (z shifted one stage, zero last move, theta kept) before the SQP; u_0 = K s + z_0
 // for the plant, and the step's z / iteration count into the caller's logs after it
@@ -309,7 +315,7 @@ struct SqpAdvanceArgs {
     double *s, *z, *bin, *X, *U, *win, *XL, *Zlog;
     int *done, *iters, *flag, *hused, *ts, *nfin, *flags, *itlog;
 };
-hipError_t launch_sqp_loop_advance(const SqpAdvanceArgs& a, hipStream_t st);
+hipError_t launch_sqp_loop_advance(const SqpAdvanceArgs& a, hipStream_t st, const PlantPar* pp = nullptr);
 hipError_t launch_sqp_loop_prep(int batch, int nx, int n, int m, int nv, int shift, const double* s,
                                 const double* bin0, const double* Bx, double* bin, double* z,
                                 hipStream_t st);

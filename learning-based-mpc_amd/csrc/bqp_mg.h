@@ -131,4 +131,115 @@ __device__ __forceinline__ void mg_plant_step(int plant, double delta, double (&
     else mg_rk4(delta, x, u);
 }
 
+// ------------------------------------------------------------------------------------------
+// The plant with per-instance coefficients (bqp_closed_loop.plant_par; models/trueModel.m:32-41
+// names them): p = [x2_c, 1/beta^2, wn^2, 2 zeta wn], in registers (the caller loads them once,
+// bqp_plant_par.h plant_par_load, before the integrator).  The nominal plant is
+// p = [0, 1, 1000, 2 sqrt(500)].  Overloads with p in front; the functions above stay as they are,
+// for the reason mg_plant_step gives: a call without parameters steps the plant to the bits it
+// always did.  The integrators are the ones above, statement for statement, on this `system`.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ void mg_system(const double (&p)[4], const double (&x)[4], double u, double (&f)[4]) {
+    f[0] = -x[1] + p[0] + 1.0 + 3.0 * (x[0] / 2.0) - (x[0] * x[0] * x[0] / 2.0);
+    f[1] = (x[0] + 1.0 - x[2] * sqrt(x[1])) * p[1];
+    f[2] = x[3];
+    f[3] = -p[2] * x[2] - p[3] * x[3] + p[2] * u;
+}
+
+__device__ __forceinline__ void mg_rk4(const double (&p)[4], double delta, double (&x)[4], double u) {
+    double k1[4], k2[4], k3[4], k4[4], y[4];
+    mg_system(p, x, u, k1);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = x[i] + delta / 2.0 * k1[i];
+    mg_system(p, y, u, k2);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = x[i] + delta / 2.0 * k2[i];
+    mg_system(p, y, u, k3);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) y[i] = x[i] + delta * k3[i];
+    mg_system(p, y, u, k4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[i] = x[i] + delta / 6.0 * (k1[i] + 2.0 * k2[i] + 2.0 * k3[i] + k4[i]);
+}
+
+__device__ __forceinline__ void mg_ode23(const double (&p)[4], double T, double (&y)[4], double u) {
+    constexpr double rtol = 1e-3, thr = 1e-6 / 1e-3;
+    constexpr double E0 = -5.0 / 72.0, E1 = 1.0 / 12.0, E2 = 1.0 / 9.0, E3 = -1.0 / 8.0;
+    const double pw = 1.0 / 3.0, hmax = 0.1 * T;
+    double F0[4], F1[4], F2[4], F3[4], ys[4], yn[4];
+    mg_system(p, y, u, F0);
+    double absh = fmin(hmax, T), rh = 0.0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) rh = fmax(rh, fabs(F0[i] / fmax(fabs(y[i]), thr)));
+    rh /= 0.8 * pow(rtol, pw);
+    if (absh * rh > 1.0) absh = 1.0 / rh;
+    double t = 0.0;
+    bool done = false;
+    for (int guard = 0; !done && guard < 4096; ++guard) {
+        const double hmin = 16.0 * (nextafter(t, INFINITY) - t);
+        absh = fmin(hmax, fmax(hmin, absh));
+        double h = absh;
+        if (1.1 * absh >= fabs(T - t)) {
+            h = T - t;
+            absh = fabs(h);
+            done = true;
+        }
+        bool nofailed = true;
+        double err = 0.0;
+        for (;; ++guard) {
+            const double h1 = h * 0.5, h2 = h * 0.75;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ys[i] = y[i] + F0[i] * h1;
+            mg_system(p, ys, u, F1);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) ys[i] = y[i] + F1[i] * h2;
+            mg_system(p, ys, u, F2);
+            const double tnew = done ? T : t + h;
+            h = tnew - t;
+            const double b0 = h * (2.0 / 9.0), b1 = h * (1.0 / 3.0), b2 = h * (4.0 / 9.0);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) yn[i] = y[i] + (F0[i] * b0 + F1[i] * b1 + F2[i] * b2);
+            mg_system(p, yn, u, F3);
+            double e = 0.0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const double fe = F0[i] * E0 + F1[i] * E1 + F2[i] * E2 + F3[i] * E3;
+                e = fmax(e, fabs(fe / fmax(fmax(fabs(y[i]), fabs(yn[i])), thr)));
+            }
+            err = absh * e;
+            if (!(err > rtol)) {
+                t = tnew;
+                break;
+            }
+            if (absh <= hmin || guard >= 4096) {
+                done = true;
+                t = tnew;
+                break;
+            }
+            absh = nofailed ? fmax(hmin, absh * fmax(0.5, 0.8 * pow(rtol / err, pw)))
+                            : fmax(hmin, 0.5 * absh);
+            nofailed = false;
+            h = absh;
+            done = false;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            y[i] = yn[i];
+            F0[i] = F3[i];
+        }
+        if (!done && nofailed) {
+            const double temp = 1.25 * pow(err / rtol, pw);
+            absh = temp > 0.2 ? absh / temp : 5.0 * absh;
+        }
+    }
+}
+
+// One sampling period of the parametrised plant.  Every kernel that steps it calls this one, as the
+// nominal kernels call the one above, so the asynchronous and the step-synchronous nonlinear MPC
+// loops stay bitwise equal with parameters too.
+__device__ __forceinline__ void mg_plant_step(const double (&p)[4], int plant, double delta, double (&x)[4], double u) {
+    if (plant == BQP_PLANT_MG_ODE23) mg_ode23(p, delta, x, u);
+    else mg_rk4(p, delta, x, u);
+}
+
 }  // namespace bqp

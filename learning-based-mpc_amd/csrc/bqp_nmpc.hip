@@ -561,8 +561,10 @@ __global__ void __launch_bounds__(64) nmpc_loop_shift_kernel(int batch, int N, i
 // of the step's solution, adds the step's disturbance to the plant's state - one addition after
 // mg_plant_step, rounded once: the state the log stores and the next solve measures - and, while
 // steps remain, copies the next step's set-point into the instance's slot of k.xr.
-template <bool TRACK>
-__global__ void __launch_bounds__(64) nmpc_loop_advance_kernel(NmpcAdvanceArgs a, NmpcTrackArgs k) {
+// PAR (bqp_closed_loop.plant_par; pp is read by those instantiations alone): the plant of the
+// instance's own step ts[b], its four coefficients loaded before the parametrised mg_plant_step.
+template <bool TRACK, bool PAR>
+__global__ void __launch_bounds__(64) nmpc_loop_advance_kernel(NmpcAdvanceArgs a, NmpcTrackArgs k, PlantPar pp) {
     __shared__ double zs[NM_WAVE * NM_CPL];
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= a.batch || !nmpc_advance_due(a, b)) return;   // uniform per wave
@@ -586,7 +588,13 @@ __global__ void __launch_bounds__(64) nmpc_loop_advance_kernel(NmpcAdvanceArgs a
 #pragma unroll
         for (int i = 0; i < 4; ++i) x[i] = a.s[(int64_t)b * 4 + i] + a.xeq[i];
         const double u = u0 + a.ueq[0];
-        mg_plant_step(a.plant, a.delta, x, u);
+        if constexpr (PAR) {
+            double p[4];
+            plant_par_load(pp, b, t, p);
+            mg_plant_step(p, a.plant, a.delta, x, u);
+        } else {
+            mg_plant_step(a.plant, a.delta, x, u);
+        }
         if constexpr (TRACK) {
             nmpc_track_disturb(k, b, t, x);
             nmpc_track_next_ref(k, a.steps, b, t);
@@ -607,7 +615,8 @@ __global__ void nmpc_track_init_kernel(int batch, NmpcTrackArgs k) {
 // what lane 0 of nmpc_loop_advance_kernel<true> does with the plant (the same inlined mg_plant_step,
 // the same single addition) and with the logs, from the solve's flags; the warm start and the
 // iteration log stay nmpc_loop_shift_kernel's, the set-point is the host's pointer into the schedule
-__global__ void nmpc_track_plant_kernel(NmpcAdvanceArgs a, NmpcTrackArgs k, int t) {
+template <bool PAR>
+__global__ void nmpc_track_plant_kernel(NmpcAdvanceArgs a, NmpcTrackArgs k, int t, PlantPar pp) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= a.batch) return;
     const double* zb = a.z + (int64_t)b * (a.N + 1);
@@ -616,7 +625,13 @@ __global__ void nmpc_track_plant_kernel(NmpcAdvanceArgs a, NmpcTrackArgs k, int 
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = a.s[(int64_t)b * 4 + i] + a.xeq[i];
     const double u = zb[0] + a.ueq[0];
-    mg_plant_step(a.plant, a.delta, x, u);
+    if constexpr (PAR) {
+        double p[4];
+        plant_par_load(pp, b, t, p);
+        mg_plant_step(p, a.plant, a.delta, x, u);
+    } else {
+        mg_plant_step(a.plant, a.delta, x, u);
+    }
     nmpc_track_disturb(k, b, t, x);
     double* Xn = a.X + ((int64_t)b * (a.steps + 1) + t + 1) * 4;
 #pragma unroll
@@ -1656,18 +1671,26 @@ hipError_t launch_nmpc_loop_shift(int batch, int N, int steps, int t, double* z,
 }
 
 static const NmpcTrackArgs nm_notrack = {};
+static const PlantPar nm_nominal = {};
 // a schedule comes with the slot array it is copied into
 static bool nmpc_track_args_ok(const NmpcTrackArgs& k) {
     return k.sref >= 0 && k.sdist >= 0 && (!k.ref) == (!k.xr);
 }
 
-hipError_t launch_nmpc_loop_advance(const NmpcAdvanceArgs& a, hipStream_t st, const NmpcTrackArgs* k) {
+hipError_t launch_nmpc_loop_advance(const NmpcAdvanceArgs& a, hipStream_t st, const NmpcTrackArgs* k,
+                                    const PlantPar* pp) {
     // the shift stages N <= 128 doubles in LDS
     if (a.batch < 1 || a.N < 1 || a.N > NMPC_MAXN || a.N > NM_WAVE * NM_CPL || a.steps < 1 ||
-        (k && !nmpc_track_args_ok(*k)))
+        (k && !nmpc_track_args_ok(*k)) || (pp && !plant_par_args_ok(*pp)))
         return hipErrorInvalidValue;
-    if (k) hipLaunchKernelGGL(nmpc_loop_advance_kernel<true>, dim3(a.batch), dim3(64), 0, st, a, *k);
-    else hipLaunchKernelGGL(nmpc_loop_advance_kernel<false>, dim3(a.batch), dim3(64), 0, st, a, nm_notrack);
+    const dim3 grid(a.batch), block(64);
+    if (pp) {
+        if (k) hipLaunchKernelGGL((nmpc_loop_advance_kernel<true, true>), grid, block, 0, st, a, *k, *pp);
+        else hipLaunchKernelGGL((nmpc_loop_advance_kernel<false, true>), grid, block, 0, st, a, nm_notrack, *pp);
+    } else {
+        if (k) hipLaunchKernelGGL((nmpc_loop_advance_kernel<true, false>), grid, block, 0, st, a, *k, nm_nominal);
+        else hipLaunchKernelGGL((nmpc_loop_advance_kernel<false, false>), grid, block, 0, st, a, nm_notrack, nm_nominal);
+    }
     return hipGetLastError();
 }
 
@@ -1677,12 +1700,15 @@ hipError_t launch_nmpc_track_init(int batch, const NmpcTrackArgs& k, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t launch_nmpc_track_plant(const NmpcAdvanceArgs& a, const NmpcTrackArgs& k, int t, hipStream_t st) {
+hipError_t launch_nmpc_track_plant(const NmpcAdvanceArgs& a, const NmpcTrackArgs& k, int t, hipStream_t st,
+                                   const PlantPar* pp) {
     // the step-synchronous loop points the solves at the schedule itself: no slot array
     if (a.batch < 1 || a.N < 1 || a.N > NMPC_MAXN || t < 0 || t >= a.steps || k.sdist < 0 || !a.z || !a.s ||
-        !a.X || !a.U || !a.flag)
+        !a.X || !a.U || !a.flag || (pp && !plant_par_args_ok(*pp)))
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(nmpc_track_plant_kernel, dim3((a.batch + 255) / 256), dim3(256), 0, st, a, k, t);
+    const dim3 grid((a.batch + 255) / 256), block(256);
+    if (pp) hipLaunchKernelGGL(nmpc_track_plant_kernel<true>, grid, block, 0, st, a, k, t, *pp);
+    else hipLaunchKernelGGL(nmpc_track_plant_kernel<false>, grid, block, 0, st, a, k, t, nm_nominal);
     return hipGetLastError();
 }
 

@@ -17,10 +17,16 @@
 #include "../../include/bqp.h"
 #include "bqp_internal.h"
 #include "bqp_mg.h"
+#include "bqp_plant_par.h"
 
 namespace bqp {
 
 // mg_system, mg_rk4, mg_ode23 and the dispatch between them (mg_plant_step): bqp_mg.h
+//
+// Per-instance plant coefficients (bqp_closed_loop.plant_par): the kernels that step the plant are
+// templates over PAR with a trailing PlantPar argument (bqp_plant_par.h).  <false> is the kernel as
+// it was and never reads the argument; <true> loads the instance's four coefficients of its step
+// into registers and calls the parametrised mg_plant_step.
 
 // s (deviation state fed to the solver) = x_init - x_eq; X[:, 0] = x_init
 __global__ void closed_loop_init_kernel(int batch, int nx, int steps, const double* xinit,
@@ -35,16 +41,24 @@ __global__ void closed_loop_init_kernel(int batch, int nx, int steps, const doub
 }
 
 // apply u_0 of the step-t solve to the plant: u = u_eq + du_0, x+ = RK4(x, u) or ode23
+template <bool PAR>
 __global__ void mg_plant_kernel(int plant, int batch, int N, int steps, int t, double delta,
                                 const double* uo, const int* fl, const double* xeq,
-                                const double* ueq, double* s, double* X, double* U, int* flags) {
+                                const double* ueq, double* s, double* X, double* U, int* flags,
+                                PlantPar pp) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= batch) return;
     double x[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) x[i] = s[(int64_t)b * 4 + i] + xeq[i];
     const double u = uo[(int64_t)b * N] + ueq[0];
-    mg_plant_step(plant, delta, x, u);
+    if constexpr (PAR) {
+        double p[4];
+        plant_par_load(pp, b, t, p);
+        mg_plant_step(p, plant, delta, x, u);
+    } else {
+        mg_plant_step(plant, delta, x, u);
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         s[(int64_t)b * 4 + i] = x[i] - xeq[i];
@@ -65,7 +79,10 @@ __global__ void mg_plant_kernel(int plant, int batch, int N, int steps, int t, d
 // ------------------------------------------------------------------------------------------
 constexpr int TRACK_THREADS = 128;
 
-__global__ void __launch_bounds__(TRACK_THREADS) track_advance_kernel(TrackArgs a, int t) {
+static const PlantPar nominal_plant = {};
+
+template <bool PAR>
+__global__ void __launch_bounds__(TRACK_THREADS) track_advance_kernel(TrackArgs a, int t, PlantPar pp) {
     const int64_t i = (int64_t)blockIdx.x * TRACK_THREADS + threadIdx.x;
     if (t >= 0 && i < a.batch) {
         const int b = (int)i;
@@ -77,7 +94,13 @@ __global__ void __launch_bounds__(TRACK_THREADS) track_advance_kernel(TrackArgs 
 #pragma unroll
             for (int k = 0; k < 4; ++k) x[k] = a.s[(int64_t)b * 4 + k] + a.xeq[k];
             const double u = a.uo[(int64_t)b * a.N] + a.ueq[0];
-            mg_plant_step(a.plant, a.delta, x, u);
+            if constexpr (PAR) {
+                double p[4];
+                plant_par_load(pp, b, t, p);
+                mg_plant_step(p, a.plant, a.delta, x, u);
+            } else {
+                mg_plant_step(a.plant, a.delta, x, u);
+            }
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 a.s[(int64_t)b * 4 + k] = x[k] - a.xeq[k];
@@ -88,13 +111,15 @@ __global__ void __launch_bounds__(TRACK_THREADS) track_advance_kernel(TrackArgs 
     if (a.nr > 0 && t + 1 < a.steps && i < (int64_t)a.batch * a.nw) track_w_entry(a, i, t + 1);
 }
 
-hipError_t launch_track_advance(const TrackArgs& a, int t, hipStream_t st) {
-    // the MG branch is written for x[4] and one input
+hipError_t launch_track_advance(const TrackArgs& a, int t, hipStream_t st, const PlantPar* pp) {
+    // the MG branch is written for x[4] and one input; the linear plant has Ap, Bp, no coefficients
     if (a.plant != BQP_PLANT_LINEAR && (a.nx != 4 || a.nu != 1)) return hipErrorInvalidValue;
+    if (pp && (a.plant == BQP_PLANT_LINEAR || !plant_par_args_ok(*pp))) return hipErrorInvalidValue;
     const int64_t n = std::max<int64_t>(t >= 0 ? a.batch : 0, a.nr > 0 && t + 1 < a.steps ? (int64_t)a.batch * a.nw : 0);
     if (n <= 0) return hipSuccess;
-    hipLaunchKernelGGL(track_advance_kernel, dim3((unsigned)((n + TRACK_THREADS - 1) / TRACK_THREADS)),
-                       dim3(TRACK_THREADS), 0, st, a, t);
+    const dim3 grid((unsigned)((n + TRACK_THREADS - 1) / TRACK_THREADS));
+    if (pp) hipLaunchKernelGGL(track_advance_kernel<true>, grid, dim3(TRACK_THREADS), 0, st, a, t, *pp);
+    else hipLaunchKernelGGL(track_advance_kernel<false>, grid, dim3(TRACK_THREADS), 0, st, a, t, nominal_plant);
     return hipGetLastError();
 }
 
@@ -232,7 +257,8 @@ __global__ void sqp_loop_u0_kernel(int batch, int nx, int n, const double* K, co
 // slowest instance of the batch had converged while the others idled.  At its last step the
 // instance stays done and nfin counts it.
 // ------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) sqp_loop_advance_kernel(SqpAdvanceArgs a) {
+template <bool PAR>
+__global__ void __launch_bounds__(256) sqp_loop_advance_kernel(SqpAdvanceArgs a, PlantPar pp) {
     const int b = blockIdx.x;
     if (b >= a.batch || !a.done[b] || a.ts[b] >= a.steps) return;     // uniform per workgroup
     const int t = a.ts[b], tid = threadIdx.x, lane = tid & 63;
@@ -252,7 +278,13 @@ __global__ void __launch_bounds__(256) sqp_loop_advance_kernel(SqpAdvanceArgs a)
 #pragma unroll
         for (int i = 0; i < 4; ++i) x[i] = sb[i] + a.xeq[i];
         const double uu = u + a.ueq[0];
-        mg_plant_step(a.plant, a.delta, x, uu);
+        if constexpr (PAR) {
+            double p[4];
+            plant_par_load(pp, b, t, p);
+            mg_plant_step(p, a.plant, a.delta, x, uu);
+        } else {
+            mg_plant_step(a.plant, a.delta, x, uu);
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             sh[i] = x[i] - a.xeq[i];
@@ -325,11 +357,12 @@ __global__ void __launch_bounds__(256) sqp_loop_advance_kernel(SqpAdvanceArgs a)
     }
 }
 
-hipError_t launch_sqp_loop_advance(const SqpAdvanceArgs& a, hipStream_t st) {
+hipError_t launch_sqp_loop_advance(const SqpAdvanceArgs& a, hipStream_t st, const PlantPar* pp) {
     // the kernel is written for the MG plant shape (x[4], one input: RK4 / ode23 of
     // models/trueModel.m, K x + c with K 1 x 4)
-    if (a.n > 4 * 256 || a.nx != 4 || a.nu != 1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(sqp_loop_advance_kernel, dim3(a.batch), dim3(256), 0, st, a);
+    if (a.n > 4 * 256 || a.nx != 4 || a.nu != 1 || (pp && !plant_par_args_ok(*pp))) return hipErrorInvalidValue;
+    if (pp) hipLaunchKernelGGL(sqp_loop_advance_kernel<true>, dim3(a.batch), dim3(256), 0, st, a, *pp);
+    else hipLaunchKernelGGL(sqp_loop_advance_kernel<false>, dim3(a.batch), dim3(256), 0, st, a, nominal_plant);
     return hipGetLastError();
 }
 
@@ -375,9 +408,13 @@ hipError_t launch_closed_loop_init(int batch, int nx, int steps, const double* x
 
 hipError_t launch_mg_plant(int plant, int batch, int N, int steps, int t, double delta,
                            const double* uo, const int* fl, const double* xeq, const double* ueq,
-                           double* s, double* X, double* U, int* flags, hipStream_t st) {
-    hipLaunchKernelGGL(mg_plant_kernel, dim3((batch + 255) / 256), dim3(256), 0, st, plant, batch, N,
-                       steps, t, delta, uo, fl, xeq, ueq, s, X, U, flags);
+                           double* s, double* X, double* U, int* flags, hipStream_t st,
+                           const PlantPar* pp) {
+    if (pp && (!plant_par_args_ok(*pp) || t < 0 || t >= steps)) return hipErrorInvalidValue;
+    if (pp) hipLaunchKernelGGL(mg_plant_kernel<true>, dim3((batch + 255) / 256), dim3(256), 0, st, plant, batch, N,
+                               steps, t, delta, uo, fl, xeq, ueq, s, X, U, flags, *pp);
+    else hipLaunchKernelGGL(mg_plant_kernel<false>, dim3((batch + 255) / 256), dim3(256), 0, st, plant, batch, N,
+                            steps, t, delta, uo, fl, xeq, ueq, s, X, U, flags, nominal_plant);
     return hipGetLastError();
 }
 
