@@ -144,6 +144,11 @@ __device__ __forceinline__ float fmar(float a, float b, float c) { return __buil
 // in fp64 only: the forced fused operation is what hipcc emits for fp64 anyway, while it does not
 // fuse every fp32 product of the sweeps, so the fp32 instantiation keeps the plain form and its bits.
 constexpr bool SWEEP_DPP_FMAC = sizeof(real) == 8;
+// A/B knob (make ab VFLAGS=-DBQP_SWEEP_ROWS=0): the fp64 sweeps' store from all lanes at one stage per
+// lane (stage_wave's solve()); 0 keeps the guarded store of row 0 everywhere
+#ifndef BQP_SWEEP_ROWS
+#define BQP_SWEEP_ROWS 1
+#endif
 #ifdef BQP_F32
 #define MADD(acc, a, b) acc = fmar((a), (b), (acc))
 #else
@@ -374,6 +379,15 @@ __device__ __forceinline__ bool hand_warm(const OcpKernelArgs& a, int inst) {
 #define STAMP(id) do { } while (0)
 #define STAMP_DECL do { } while (0)
 #define STAMP_STORE(base) do { } while (0)
+#endif
+
+// diagnostic build with -DBQP_STAMPS_SPLIT as well: the first pass of solve() split into right-hand
+// side (slot 2, otherwise empty), pre-pass bodies (slot 15, otherwise the polish) and the trailing
+// wave_sync (slot 10); tools/stamps.py --split names them
+#if defined(BQP_STAMPS) && defined(BQP_STAMPS_SPLIT)
+#define STAMP_SPLIT(id) STAMP(id)
+#else
+#define STAMP_SPLIT(id) do { } while (0)
 #endif
 
 #define BARRIER() __syncthreads()
@@ -1136,8 +1150,38 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     // right-hand side q = r_v + C'((lam o ri - rc)/t): the row wave supplies the box terms
     // [upper, lower] per stage (ebox) and Fp'e (gpe); direction written to (ods, odu)
     const int li = lane < NS ? lane : NS - 1;
-    auto solve = [&](int ods, int odu) __attribute__((always_inline)) {
+    constexpr bool SWEEP_ROWS = BQP_SWEEP_ROWS && SWEEP_DPP_FMAC && SPL == 1;
+    // The repair kernels of the (2, 2, 2) family sit at 255 of 256 VGPRs.  With the stage-0 offsets
+    // carried across the sweep loops for the peeled pair, and the entry index across the solve, one
+    // of their long-lived addresses went to scratch (8 B).  There the entry index is formed inside
+    // each sweep and the peeled pair and the odd stage are reached from the walked offsets (252
+    // VGPRs, no scratch).  Only there: in the MG repair kernel that form made the compiler split
+    // the walked offsets into a shared part and three differences, five instructions more per trip.
+    constexpr bool SWEEP_TAIL_WALK = SWEEP_ROWS && POL && NX == 2;
+    auto solve =[&](int ods, int odu) __attribute__((always_inline)) {
         const int lane = opq(lane_w);
+        // the sweeps' entry index.  SWEEP_ROWS (fp64, one stage per lane: N + 1 <= 64): every
+        // 16-lane row runs the recursion on entry min(lane mod 16, NS - 1) with its own start
+        // values, so every lane holds the right bits of its entry and stores them - the store
+        // needs no guard and the sweeps no EXEC write.  That is right only with all 64 lanes
+        // enabled here (a disabled lane reads as 0 through DPP, and the rows would differ).  They
+        // are: the kernels are launched with whole waves; a wave leaves ocp_body as a whole (the
+        // batch, redo, repair and skip tests are on the wave's instance) or enters stage_wave as a
+        // whole (the wave index picks stage or row wave), in the plain, queue and repair kernels
+        // alike; and every branch and loop exit of stage_wave around a solve() - the hand-over
+        // start, the stop test (combine() and the exchange words are the same in every lane,
+        // factor()'s pivots are formed by every quad from the same operands), the polish's
+        // decisions (exchange words) - is on a value that is the same in all lanes.  Two stages
+        // per lane (SPL = 2) keep row 0 and the guarded store.
+        const int sweep_lx = SWEEP_ROWS ? ((lane & 15) < NS ? (lane & 15) : NS - 1) : li;
+        auto sweep_entry = [&]() __attribute__((always_inline)) -> int {
+            if constexpr (SWEEP_TAIL_WALK) {
+                const int l16 = opq(lane_w) & 15;
+                return l16 < NS ? l16 : NS - 1;
+            } else {
+                return sweep_lx;
+            }
+        };
         real qs[SPL][G > 1 ? ES : NS], qu[SPL][NU];
         if constexpr (G > 1) {
             const lanes::StageLane sl = lanes::stage_lane(lane, N, G);
@@ -1172,6 +1216,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                     for (int i = 0; i < NU; ++i) qu[0][i] += W[L.gpe + NS + i];
                 }
             }
+            STAMP_SPLIT(2);
             if (k < N) {
                 const real* Kk = W + L.K + k * NU * NS;
 #pragma unroll
@@ -1187,6 +1232,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
 #pragma unroll
                 for (int t = 0; t < ES; ++t) W[L.pv + N * NS + ei[t]] = qs[0][t];
             }
+            STAMP_SPLIT(15);
         } else {
         real gpe[NV];
 #pragma unroll
@@ -1228,6 +1274,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 }
             }
         }
+        STAMP_SPLIT(2);
         // pre-pass: qh_k = qt_k + cw_k with qt_k = qs_k + K_k' qu_k (cw_k = Phi_k' P_{k+1} re_k
         // is the right-hand-side-independent part, formed once per factorisation by
         // prep_iter); p_N = qs_N.  qh carries everything of the backward recursion that does
@@ -1251,6 +1298,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 for (int i = 0; i < NS; ++i) W[L.pv + N * NS + i] = qs[j][i];
             }
         }
+        STAMP_SPLIT(15);
         }
         wave_sync();
         STAMP(10);
@@ -1275,7 +1323,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             // (fmac_rbc_chain, bqp_wave.h: lane c of the row is the multiplicand of entry c), so
             // the vector is never copied out into p[]; the start value is one entry per lane.
             // Lanes >= NS of a row never feed a lane < NS.
-            const int lx = li;
+            const int lx = sweep_entry();
             real pv = W[L.pv + N * NS + lx];
             real Acol[NS];
 #pragma unroll
@@ -1319,41 +1367,79 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 acc = fmac_rbc_chain(acc, pv, ph);
                 pv = acc;
             };
-            auto store_b = [&](int k) __attribute__((always_inline)) {
-                if (lane < NS) W[L.pv + k * NS + lane] = pv;
+            // The operands are reached through per-lane word offsets that walk with the stage
+            // (round 10): oK / oQ / oS are entry lx of K_k, qh_k and p_k at the lowest stage a trip
+            // touches, advanced by a constant once per trip, and every access of the trip is an
+            // immediate offset from them - no stage index is turned into an address inside the
+            // loop.  The clamp of the refills' stage index is gone by peeling: the loop runs the
+            // trips whose refills (stages k - 2, k - 3) exist, the last pair follows it with the
+            // one read it needs (stage 0 into set 0, the operands of an odd N's last stage; for an
+            // even N the read the clamp made, unused).  No read leaves the arrays: the lowest
+            // offset dereferenced is stage 0's.  Header waits as before: on every path into the
+            // loop header and into the peeled pair both sets' loads are in flight.
+            auto store_b = [&](int o) __attribute__((always_inline)) {
+                if constexpr (SWEEP_ROWS) W[o] = pv;
+                else if (lane < NS) W[o] = pv;
             };
-            auto load_k = [&](int k, real (&kc)[NU]) __attribute__((always_inline)) {
+            auto load_k = [&](int o, real (&kc)[NU]) __attribute__((always_inline)) {
 #pragma unroll
-                for (int x = 0; x < NU; ++x) kc[x] = W[L.K + k * NU * NS + x * NS + lx];
+                for (int x = 0; x < NU; ++x) kc[x] = W[o + x * NS];
             };
-            auto load_q = [&](int k, real& q) __attribute__((always_inline)) {
-                q = W[L.qt_xpi + k * NS + lx];
-            };
+            constexpr int KS = NU * NS;
+            const int bK = L.K + lx, bQ = L.qt_xpi + lx, bS = L.pv + lx;   // stage 0
             real k0[NU], q0, k1[NU], q1;
             MB m0, m1;
-            load_k(N - 1, k0);
-            load_q(N - 1, q0);
+            load_k(bK + (N - 1) * KS, k0);
+            q0 = W[bQ + (N - 1) * NS];
             load_mb(N - 1, m0);
-            load_k(max(N - 2, 0), k1);
-            load_q(max(N - 2, 0), q1);
-            load_mb(max(N - 2, 0), m1);
-            auto step_b = [&](int k, const real (&kc)[NU], real q, const MB& m) __attribute__((always_inline)) {
+            const int kn = max(N - 2, 0);
+            load_k(bK + kn * KS, k1);
+            q1 = W[bQ + kn * NS];
+            load_mb(kn, m1);
+            auto step_b = [&](int o, const real (&kc)[NU], real q, const MB& m) __attribute__((always_inline)) {
                 real ph[NS];
                 phi_b(kc, m, ph);
                 chain_b(ph, q);
-                store_b(k);
+                store_b(o);
             };
-            for (int k = N - 1; k >= 1; k -= 2) {
-                step_b(k, k0, q0, m0);
-                load_k(max(k - 2, 0), k0);
-                load_q(max(k - 2, 0), q0);
-                load_mb(max(k - 2, 0), m0);
-                step_b(k - 1, k1, q1, m1);
-                load_k(max(k - 3, 0), k1);
-                load_q(max(k - 3, 0), q1);
-                load_mb(max(k - 3, 0), m1);
+            // stage k - 3 of the trip (only formed as integers: nothing is read below stage 0)
+            int oK = bK + (N - 4) * KS, oQ = bQ + (N - 4) * NS, oS = bS + (N - 4) * NS;
+            int k = N - 1;
+            for (; k >= 3; k -= 2) {
+                step_b(oS + 3 * NS, k0, q0, m0);
+                load_k(oK + KS, k0);
+                q0 = W[oQ + NS];
+                load_mb(k - 2, m0);
+                step_b(oS + 2 * NS, k1, q1, m1);
+                load_k(oK, k1);
+                q1 = W[oQ];
+                load_mb(k - 3, m1);
+                oK -= 2 * KS;
+                oQ -= 2 * NS;
+                oS -= 2 * NS;
             }
-            if (N & 1) step_b(0, k0, q0, m0);
+            if constexpr (SWEEP_TAIL_WALK) {
+                // the offsets stand at stage k - 3, k = 2 (odd N), 1 (even N) or 0 (N = 1)
+                const int z = 3 - k;                          // stages from the offsets up to stage 0
+                if (N >= 2) {                                 // the last pair: stages k, k - 1
+                    step_b(oS + 3 * NS, k0, q0, m0);
+                    load_k(oK + z * KS, k0);
+                    q0 = W[oQ + z * NS];
+                    load_mb(0, m0);
+                    step_b(oS + 2 * NS, k1, q1, m1);
+                }
+                if (N & 1) step_b(oS + z * NS, k0, q0, m0);
+            } else {
+            if (N >= 2) {
+                const int kl = 1 + (N & 1);               // the last pair: stages kl, kl - 1
+                step_b(bS + kl * NS, k0, q0, m0);
+                load_k(bK, k0);
+                q0 = W[bQ];
+                load_mb(0, m0);
+                step_b(bS + (kl - 1) * NS, k1, q1, m1);
+            }
+            if (N & 1) step_b(bS, k0, q0, m0);   // set 0 holds stage 0 (N = 1: from the first load)
+            }
             } else {
             real Acol[NS];
 #pragma unroll
@@ -1483,7 +1569,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             if constexpr (SWEEP_DPP_FMAC) {
             // fp64, as the backward sweep: the previous accumulator is the DPP operand of the
             // multiply-adds; the start value is entry lx of ds_0 = (0, theta_0 step) per lane
-            const int lx = li;
+            const int lx = sweep_entry();
             real dv = 0.0;
 #pragma unroll
             for (int x = 0; x < NP; ++x) dv = (lx == NX + x) ? r0[x] : dv;
@@ -1523,38 +1609,74 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 acc = fmac_rbc_chain(acc, dv, ph);
                 dv = acc;
             };
-            auto store_f = [&](int k) __attribute__((always_inline)) {
-                if (lane < NS) W[ods + (k + 1) * NS + lane] = dv;
+            // walked per-lane offsets and a peeled last pair, as in the backward sweep: oK (the
+            // whole K_k: the same in every lane, kept in a vector register so that it is advanced
+            // by one add per trip), oF and oS (entry lx of f_k and of ds_k) stand at the trip's
+            // first stage k; the loop runs the trips whose refills (stages k + 2, k + 3) exist,
+            // the last pair reads stage N - 1 into set 0 (the operands of an odd N's last stage)
+            auto store_f = [&](int o) __attribute__((always_inline)) {
+                if constexpr (SWEEP_ROWS) W[o] = dv;
+                else if (lane < NS) W[o] = dv;
             };
-            auto load_fk = [&](int k, real& f) __attribute__((always_inline)) {
-                f = W[L.fv + k * NS + lx];
+            auto load_kw = [&](int o, real (&kr)[NU][NS]) __attribute__((always_inline)) {
+#pragma unroll
+                for (int x = 0; x < NU; ++x)
+#pragma unroll
+                    for (int c = 0; c < NS; ++c) kr[x][c] = W[o + x * NS + c];
             };
-            // unconditional refills (stage index clamped at N - 1) and whole stage pairs, as in
-            // the backward sweep
+            constexpr int KS = NU * NS;
+            const int bK = opq(L.K), bF = L.fv + lx, bS = ods + lx;        // stage 0
             MF m0, m1;
-            load_k(0, k0);
-            load_fk(0, f0);
+            load_kw(bK, k0);
+            f0 = W[bF];
             load_mf(0, m0);
-            load_k(min(1, N - 1), k1);
-            load_fk(min(1, N - 1), f1);
-            load_mf(min(1, N - 1), m1);
-            auto step_f = [&](int k, const real (&kr)[NU][NS], real f, const MF& m) __attribute__((always_inline)) {
+            const int kn = min(1, N - 1);
+            load_kw(bK + kn * KS, k1);
+            f1 = W[bF + kn * NS];
+            load_mf(kn, m1);
+            auto step_f = [&](int o, const real (&kr)[NU][NS], real f, const MF& m) __attribute__((always_inline)) {
                 real ph[NS];
                 phi_f(kr, m, ph);
                 chain_f(ph, f);
-                store_f(k);
+                store_f(o);
             };
-            for (int k = 0; k + 1 < N; k += 2) {
-                step_f(k, k0, f0, m0);
-                load_k(min(k + 2, N - 1), k0);
-                load_fk(min(k + 2, N - 1), f0);
-                load_mf(min(k + 2, N - 1), m0);
-                step_f(k + 1, k1, f1, m1);
-                load_k(min(k + 3, N - 1), k1);
-                load_fk(min(k + 3, N - 1), f1);
-                load_mf(min(k + 3, N - 1), m1);
+            int oK = bK, oF = bF, oS = bS;
+            int k = 0;
+            for (; k + 3 < N; k += 2) {
+                step_f(oS + NS, k0, f0, m0);
+                load_kw(oK + 2 * KS, k0);
+                f0 = W[oF + 2 * NS];
+                load_mf(k + 2, m0);
+                step_f(oS + 2 * NS, k1, f1, m1);
+                load_kw(oK + 3 * KS, k1);
+                f1 = W[oF + 3 * NS];
+                load_mf(k + 3, m1);
+                oK += 2 * KS;
+                oF += 2 * NS;
+                oS += 2 * NS;
             }
-            if (N & 1) step_f(N - 1, k0, f0, m0);
+            if constexpr (SWEEP_TAIL_WALK) {
+                // the offsets stand at stage k = N - 2 - (N & 1) (N = 1: 0)
+                const int z = N - 1 - k;                      // stages from the offsets up to stage N - 1
+                if (N >= 2) {                                 // the last pair: stages k, k + 1
+                    step_f(oS + NS, k0, f0, m0);
+                    load_kw(oK + z * KS, k0);
+                    f0 = W[oF + z * NS];
+                    load_mf(N - 1, m0);
+                    step_f(oS + 2 * NS, k1, f1, m1);
+                }
+                if (N & 1) step_f(oS + (z + 1) * NS, k0, f0, m0);
+            } else {
+            if (N >= 2) {
+                const int kl = N - 2 - (N & 1);           // the last pair: stages kl, kl + 1
+                step_f(bS + (kl + 1) * NS, k0, f0, m0);
+                load_kw(bK + (N - 1) * KS, k0);
+                f0 = W[bF + (N - 1) * NS];
+                load_mf(N - 1, m0);
+                step_f(bS + (kl + 2) * NS, k1, f1, m1);
+            }
+            if (N & 1) step_f(bS + N * NS, k0, f0, m0);   // set 0 holds stage N - 1
+            }
             } else {
             real Arow[NS], Bli[NU];
 #pragma unroll

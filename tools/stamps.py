@@ -1,11 +1,13 @@
 """Diagnostic: per-phase cycle shares of the structured kernel (build: make -C learning-based-mpc_amd stamps).
 Runs the C2 workload through libbqp_stamps.so and prints the mean cycles per phase per instance.
 
-    python tools/stamps.py [BATCH] [--json OUT.json]
+    python tools/stamps.py [BATCH] [--json OUT.json] [--split]
 
 --json writes the summary bench.py reports as roofline.latency (stage-wave busy fraction and
 cycles per iteration), tagged with the sha1 of csrc/bqp_ocp.hip so that bench can tell whether
-the stamps were taken on the kernel source it runs."""
+the stamps were taken on the kernel source it runs.  --split: for a build with -DBQP_STAMPS_SPLIT as
+well, which stamps the first pass of solve() in three parts (right-hand side, pre-pass bodies, the
+wave_sync behind them)."""
 import ctypes as C
 import hashlib
 import json
@@ -23,8 +25,11 @@ _lib.LIB_PATH = os.environ.get('BQP_STAMPS_LIB') or os.path.join(ROOT, 'learning
 lib = _lib.load()
 lib.bqp_debug_stamps.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _lib._PD]
 import bench
+split = '--split' in sys.argv
 pos = [a for a in sys.argv[1:] if not a.startswith('--')]
 jout = sys.argv[sys.argv.index('--json') + 1] if '--json' in sys.argv else None
+if split and jout:
+    sys.exit('--split stamps are not comparable with the plain build: no --json with --split')
 cfg = sys.argv[sys.argv.index('--config') + 1] if '--config' in sys.argv else 'C2'
 for o in (jout, cfg):
     if o in pos:
@@ -45,6 +50,10 @@ stage = ['wait B0 + residual combine', 'combine', 'wait B1', 'decide + factor', 
          'solve pred (post-fwd)', 'wait B3,B4', 'solve corr (post-fwd)', 'wait B5,B6', 'update + partials',
          'solves: rhs + pre-pass', 'solves: backward sweep', 'solves: post-backward',
          'solves: theta + forward sweep', 'solves: post-forward']
+if split:
+    stage[2] = 'solves: rhs'
+    stage[10] = 'solves: wave_sync behind the pre-pass'
+    stage.append('solves: pre-pass bodies')
 row = ['wait B0', 'row residuals', 'rhs pred', 'wait B1,B2', 'wait B3',
        'pred pass/sigma/rhs corr', 'wait B4,B5', 'ratio corr + box apply', 'wait B6 + poly apply/lam side']
 ms, _ = h.kernel_ms()
