@@ -149,6 +149,12 @@ constexpr bool SWEEP_DPP_FMAC = sizeof(real) == 8;
 #ifndef BQP_SWEEP_ROWS
 #define BQP_SWEEP_ROWS 1
 #endif
+// A/B knob (make ab VFLAGS=-DBQP_FACTOR_ROWS=0): the fp64 Riccati factorisation with P_{k+1} held
+// in lanes, one packed entry per lane of every 16-lane row (stage_wave's factor()); 0 keeps the
+// quad / LDS form everywhere.  fp32 and two stages per lane (SPL = 2) keep that form in any case.
+#ifndef BQP_FACTOR_ROWS
+#define BQP_FACTOR_ROWS 1
+#endif
 #ifdef BQP_F32
 #define MADD(acc, a, b) acc = fmar((a), (b), (acc))
 #else
@@ -383,11 +389,16 @@ __device__ __forceinline__ bool hand_warm(const OcpKernelArgs& a, int inst) {
 
 // diagnostic build with -DBQP_STAMPS_SPLIT as well: the first pass of solve() split into right-hand
 // side (slot 2, otherwise empty), pre-pass bodies (slot 15, otherwise the polish) and the trailing
-// wave_sync (slot 10); tools/stamps.py --split names them
+// wave_sync (slot 10); tools/stamps.py --split names them.
+// The main loop's slot 3 (decide + factor + prep_iter) is closed behind factor() instead, so
+// that the factorisation's cycles stand alone; prep_iter() then falls into slot 4 (the wait at B2,
+// which is short: the row wave sits at that barrier for the whole phase)
 #if defined(BQP_STAMPS) && defined(BQP_STAMPS_SPLIT)
 #define STAMP_SPLIT(id) STAMP(id)
+#define STAMP_PLAIN(id) do { } while (0)
 #else
 #define STAMP_SPLIT(id) do { } while (0)
+#define STAMP_PLAIN(id) STAMP(id)
 #endif
 
 #define BARRIER() __syncthreads()
@@ -777,13 +788,35 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     // (ds_read_b128 broadcasts).  Per stage: one dot product per lane, one LDS round trip.
     // Same association as oracle/cpu_ipm.c factor(): partial sums over m mod 4,
     // (s0 + s1) + (s2 + s3), then Ht + sum.
+    //
+    // FACTOR_ROWS (fp64, one stage per lane): the same recursion with the transposed layout and
+    // P_{k+1} kept in lanes.  Lane l of EVERY 16-lane row owns packed entry e = min(l, NPK - 1), and
+    // row r = lane / 16 takes the part of lane r of the quad: values r, r + 4, ... of that entry,
+    // with the same per-lane coefficient rows.  P_{k+1}(e) is one register per lane, so a stage's
+    // dot product reads it as the DPP operand of its multiply-adds (fmac_rbc_dot4: row_newbcast:m
+    // is entry m) - no packed copy in 2 PST registers, no read-back.  The VAL values of an entry sit
+    // in the four rows and are exchanged with the row swaps (xrow_gather, VALU only); then every
+    // lane of every row does the stage arithmetic on the same operands, so all rows end the stage
+    // with P_k(e) in lane l (lanes >= NPK: the bits of lane NPK - 1), and `ok` is the same in all
+    // lanes.  The stores for the later passes (P_k, K_k, the factor of R^_k) come from every lane
+    // without a guard: two lanes that write one address write the same bits (K_k's column je and
+    // the factor depend on je and on M_uu alone, formed by the same operations on the same
+    // operands in every lane that holds them).  Nothing in the loop reads them back, so a stage
+    // has no LDS round trip, no wave barrier and no EXEC write.  Hazards: the first DPP read of a
+    // stage follows the write of P_k by two wait states (inside fmac_rbc_dot4); the swaps and the
+    // theta block's rbc are builtins, whose wait states the compiler places.  As the sweeps' row
+    // form, this is right only with all 64 lanes enabled (see factor()).
     constexpr int PST = pk_stride(NS);
     constexpr int NPK = pk_len(NS);
     constexpr int NUT = NU * (NU + 1) / 2;
     constexpr int VAL = 1 + 2 * NU + NUT;           // values one P_k entry needs
-    constexpr int VPL = (VAL + 3) / 4;              // values per lane of the quad
+    constexpr int VPL = (VAL + 3) / 4;              // values per lane of the quad (FACTOR_ROWS: per row)
+    constexpr bool FACTOR_ROWS = BQP_FACTOR_ROWS && sizeof(real) == 8 && SPL == 1;
     static_assert(4 * NPK <= WAVE, "one quad per packed entry of P");
-    const int fq = lane >> 2, fql = lane & 3;
+    static_assert(!FACTOR_ROWS || NPK <= 16, "FACTOR_ROWS: one packed entry of P per lane of a row");
+    static_assert(!FACTOR_ROWS || NP <= 2, "FACTOR_ROWS: the theta block's entries are taken one by one");
+    const int fq = FACTOR_ROWS ? ((lane & 15) < NPK ? (lane & 15) : NPK - 1) : lane >> 2;
+    const int fql = FACTOR_ROWS ? lane >> 4 : lane & 3;
     const bool fquad = fq < NPK;
     int ie = 0, je = 0;                             // packed entry fq -> (ie <= je)
     {
@@ -895,17 +928,31 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
     };
     auto Pm = [&](int a_, int b_) __attribute__((always_inline)) -> real { return pu[pk_idx(NS, a_, b_)]; };
     auto factor = [&]() __attribute__((always_inline)) -> bool {
+        // FACTOR_ROWS needs all 64 lanes enabled: a disabled lane reads as 0 through the DPP
+        // operands and the row swaps, and the rows would no longer agree.  They are enabled at the
+        // three call sites - the start, the main loop behind the stop test, the polish's m != 1
+        // branch - by the argument solve() gives for its own: whole waves enter stage_wave, and each
+        // of the three sits behind branches on values that are the same in every lane (the
+        // hand-over start is on the instance; flag, stop and the stop test's operands come from
+        // combine() and the exchange words; m, rd and dec follow exchange words and factor()'s own
+        // result, which is the same in all lanes in either form).
         HRaw raw, nxt;
+        real pl = 0;                                  // FACTOR_ROWS: P_{k+1}(fq), in every row
         {
             // P_N = Ht_N(s, s)
             load_h(N, raw);
             const real v0 = ht(N, raw, 0);
+            if constexpr (FACTOR_ROWS) {
+                pl = xrow_bcast<0>(v0);               // value 0 is row 0's
+                W[L.P + N * PST + fq] = pl;
+            } else {
             if (fquad && fql == 0) {
                 W[L.P + (LNG ? (N & 1) : N) * PST + fq] = v0;
                 if constexpr (LNG) Pgl[N * PST + fq] = v0;
             }
+            }
         }
-        read_p(N);
+        if constexpr (!FACTOR_ROWS) read_p(N);
         bool ok = true;
         // one stage of the recursion: P_k from P_{k+1} (in pu) and the stage's raw operands
         auto fstage = [&](int k, const HRaw& raw) __attribute__((always_inline)) {
@@ -913,7 +960,21 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
 #pragma unroll
             for (int t = 0; t < VPL; ++t) {
                 real sp0 = 0, sp1 = 0, sp2 = 0, sp3 = 0;
-                if constexpr (STG) {
+                if constexpr (FACTOR_ROWS) {
+                    real sp[4];
+                    if constexpr (STG) {
+                        real cm[NPK];
+                        int m = 0;
+#pragma unroll
+                        for (int a_ = 0; a_ < NS; ++a_)
+#pragma unroll
+                            for (int b = a_; b < NS; ++b, ++m) cm[m] = cf_at(raw, t, a_, b);
+                        fmac_rbc_dot4(sp, pl, cm);
+                    } else {
+                        fmac_rbc_dot4(sp, pl, cf[t]);
+                    }
+                    sp0 = sp[0]; sp1 = sp[1]; sp2 = sp[2]; sp3 = sp[3];
+                } else if constexpr (STG) {
                     int m = 0;
 #pragma unroll
                     for (int a_ = 0; a_ < NS; ++a_)
@@ -937,7 +998,17 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 mv[t] = ht(k, raw, t) + ((sp0 + sp1) + (sp2 + sp3));
             }
             // gather the VAL values in lane 4e: value v sits in lane v % 4, slot v / 4
+            // (FACTOR_ROWS: in every lane; value v sits in row v % 4, slot v / 4)
             real g[VAL];
+            if constexpr (FACTOR_ROWS) {
+#pragma unroll
+                for (int t = 0; t < VPL; ++t) {
+                    real g4[4];
+                    xrow_gather(mv[t], g4);
+#pragma unroll
+                    for (int s = 0; s < 4; ++s) if (4 * t + s < VAL) g[4 * t + s] = g4[s];
+                }
+            } else {
 #pragma unroll
             for (int v = 0; v < VAL; ++v) {
                 const int s = v & 3;
@@ -946,6 +1017,7 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                      : (s == 1) ? dpp_mov0<0x55>(src)
                      : (s == 2) ? dpp_mov0<0xAA>(src)
                                 : dpp_mov0<0xFF>(src);
+            }
             }
             real pv, Kc[NU], Lf[NU * NU];
             if constexpr (NU == 1) {
@@ -971,13 +1043,34 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
                 real y[NU];
 #pragma unroll
                 for (int x = 0; x < NU; ++x) y[x] = g[1 + NU + x];   // M(je, u)
-                chol_solve_small<NU>(Lf, y);
+                if constexpr (FACTOR_ROWS && NU == 2) {
+                    // chol_solve_small with its one ambiguous contraction written out.  Left to
+                    // the compiler, b0 L0 - L2 w1 was fused as fma(L0, b0, -(L2 w1)) in the quad
+                    // form and as fma(L2, -w1, b0 L0) here, where -w1 is at hand for the store of
+                    // K_k: one rounding apart.  The quad form's choice is kept (round 11).
+                    const real w1 = (y[1] - Lf[2] * y[0]) * Lf[3];
+                    y[0] = fmar(y[0], Lf[0], -(Lf[2] * w1));
+                    y[1] = w1;
+                } else {
+                    chol_solve_small<NU>(Lf, y);
+                }
                 real acc = g[1] * y[0];
 #pragma unroll
                 for (int x = 1; x < NU; ++x) acc = fmar(g[1 + x], y[x], acc);
                 pv = g[0] - acc;
 #pragma unroll
                 for (int x = 0; x < NU; ++x) Kc[x] = -y[x];
+            }
+            if constexpr (FACTOR_ROWS) {
+                // every lane: the same bits to an address from all lanes that write it; nothing
+                // of this loop reads them back
+                W[L.P + k * PST + fq] = pv;
+#pragma unroll
+                for (int x = 0; x < NU; ++x) W[L.K + k * NU * NS + x * NS + je] = Kc[x];
+#pragma unroll
+                for (int x = 0; x < NU * NU; ++x) W[L.Lr + k * NU * NU + x] = Lf[x];
+                pl = pv;
+                return;
             }
             if (fquad && fql == 0) {
                 W[L.P + (LNG ? (k & 1) : k) * PST + fq] = pv;
@@ -1022,7 +1115,15 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
 #pragma unroll
         for (int x = 0; x < NP; ++x)
 #pragma unroll
-            for (int y = 0; y < NP; ++y) Pt[x][y] = Pm(NX + x, NX + y);
+            for (int y = 0; y < NP; ++y) Pt[x][y] = FACTOR_ROWS ? real(0) : Pm(NX + x, NX + y);
+        if constexpr (FACTOR_ROWS) {
+            // P_0 is in lanes: its theta block by row broadcasts of the entries
+            Pt[0][0] = rbc<pk_idx(NS, NX, NX)>(pl);
+            if constexpr (NP == 2) {
+                Pt[0][1] = Pt[1][0] = rbc<pk_idx(NS, NX, NX + 1)>(pl);
+                Pt[1][1] = rbc<pk_idx(NS, NX + 1, NX + 1)>(pl);
+            }
+        }
         if constexpr (NP == 1) {
             ok = ok && (Pt[0][0] > 0.0);
             L0[0][0] = 1.0 / Pt[0][0];
@@ -1890,8 +1991,9 @@ __device__ __forceinline__ void stage_wave(const OcpKernelArgs& a, real* W, cons
             if (it == max_iter) stop = true;
         }
         if (!stop && !factor()) { flag = -8; stop = true; }
+        STAMP_SPLIT(3);
         if (!stop) prep_iter();
-        STAMP(3);
+        STAMP_PLAIN(3);
         if (lane == 0) {
             X[X_STOP] = stop ? 1.0 : 0.0;
             X[X_FEASOK] = (feas <= FEAS_GUARD * (1.0 + bscale)) ? 1.0 : 0.0;

@@ -251,6 +251,68 @@ __device__ __forceinline__ T fmac_rbc_chain(T q, T v, const T (&ph)[NC]) {
 #undef BQP_CHAIN_HEAD
 #undef BQP_FMAC_RBC
 
+// The dot product of a Riccati factor stage (stage_wave's factor(), FACTOR_ROWS): lane m of every
+// 16-lane row holds entry m of a vector v, and each lane has NC coefficients of its own.  Forms the
+// four partial sums s_j = sum over m = j mod 4 of c[m] * (lane m of v), each from 0 in the order of
+// m, as fma(c[m], v_m, s_j): the caller adds them as (s0 + s1) + (s2 + s3).  NC = 10, 15 (the model
+// families' packed P: NS = 4, 5) are ONE asm statement:
+//  - the four accumulators are independent, so the scheduler would be free to reorder separate
+//    statements, and the one that must wait for v's writer would no longer be known;
+//  - the four zero writes in front are the 2 wait states between a VALU write of v and its first
+//    DPP read (fmac_rbc's first hazard), so the statement needs no s_nop at all: consecutive
+//    multiply-adds are on different accumulators, and each reads its accumulator as a plain operand.
+// A source lane that is disabled reads as 0 (bound_ctrl:1): callers run with all lanes enabled.
+#define BQP_DOT4_ZERO \
+    "v_mov_b64 %0, 0\n\tv_mov_b64 %1, 0\n\tv_mov_b64 %2, 0\n\tv_mov_b64 %3, 0\n\t"
+#define BQP_DOT4_FMAC(ACC, OP, C) \
+    "v_fmac_f64_dpp %" #ACC ", %4, %" #OP " row_newbcast:" #C " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
+template <int M, int NC, typename T>
+__device__ __forceinline__ void fmac_rbc_dot4_seq(T (&s)[4], T v, const T (&c)[NC]) {
+    fmac_rbc<M, (M < 4)>(s[M & 3], v, c[M]);   // the first of each accumulator may follow v's writer
+    if constexpr (M + 1 < NC) fmac_rbc_dot4_seq<M + 1, NC>(s, v, c);
+}
+template <int NC, typename T>
+__device__ __forceinline__ void fmac_rbc_dot4(T (&s)[4], T v, const T (&c)[NC]) {
+    static_assert(sizeof(T) == 8, "fmac_rbc_dot4: fp64 only");
+    static_assert(NC >= 4 && NC <= 16, "fmac_rbc_dot4: one entry per lane of a 16-lane row");
+    if constexpr (NC == 10) {
+        asm(BQP_DOT4_ZERO
+            BQP_DOT4_FMAC(0, 5, 0) BQP_DOT4_FMAC(1, 6, 1) BQP_DOT4_FMAC(2, 7, 2) BQP_DOT4_FMAC(3, 8, 3)
+            BQP_DOT4_FMAC(0, 9, 4) BQP_DOT4_FMAC(1, 10, 5) BQP_DOT4_FMAC(2, 11, 6) BQP_DOT4_FMAC(3, 12, 7)
+            BQP_DOT4_FMAC(0, 13, 8) BQP_DOT4_FMAC(1, 14, 9)
+            : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3])
+            : "v"(v), "v"(c[0]), "v"(c[1]), "v"(c[2]), "v"(c[3]), "v"(c[4]), "v"(c[5]), "v"(c[6]),
+              "v"(c[7]), "v"(c[8]), "v"(c[9]));
+    } else if constexpr (NC == 15) {
+        asm(BQP_DOT4_ZERO
+            BQP_DOT4_FMAC(0, 5, 0) BQP_DOT4_FMAC(1, 6, 1) BQP_DOT4_FMAC(2, 7, 2) BQP_DOT4_FMAC(3, 8, 3)
+            BQP_DOT4_FMAC(0, 9, 4) BQP_DOT4_FMAC(1, 10, 5) BQP_DOT4_FMAC(2, 11, 6) BQP_DOT4_FMAC(3, 12, 7)
+            BQP_DOT4_FMAC(0, 13, 8) BQP_DOT4_FMAC(1, 14, 9) BQP_DOT4_FMAC(2, 15, 10) BQP_DOT4_FMAC(3, 16, 11)
+            BQP_DOT4_FMAC(0, 17, 12) BQP_DOT4_FMAC(1, 18, 13) BQP_DOT4_FMAC(2, 19, 14)
+            : "=&v"(s[0]), "=&v"(s[1]), "=&v"(s[2]), "=&v"(s[3])
+            : "v"(v), "v"(c[0]), "v"(c[1]), "v"(c[2]), "v"(c[3]), "v"(c[4]), "v"(c[5]), "v"(c[6]),
+              "v"(c[7]), "v"(c[8]), "v"(c[9]), "v"(c[10]), "v"(c[11]), "v"(c[12]), "v"(c[13]),
+              "v"(c[14]));
+    } else {
+        s[0] = s[1] = s[2] = s[3] = T(0);
+        fmac_rbc_dot4_seq<0, NC>(s, v, c);       // any other length: one statement per multiply-add
+    }
+}
+#undef BQP_DOT4_FMAC
+#undef BQP_DOT4_ZERO
+
+// the values of the four 16-lane rows (lane 16 q + l%16, q = 0..3) in lane l of every row: the
+// four xrow_bcast<q> sharing their swaps (one v_permlane16_swap pair, two v_permlane32_swap pairs)
+template <typename T>
+__device__ __forceinline__ void xrow_gather(T v, T (&g)[4]) {
+    T a = v, b = v;
+    pl16_swap(a, b);                 // a: rows (0, 0, 2, 2), b: rows (1, 1, 3, 3)
+    g[0] = a; g[2] = a;
+    pl32_swap(g[0], g[2]);           // row 0 everywhere, row 2 everywhere
+    g[1] = b; g[3] = b;
+    pl32_swap(g[1], g[3]);           // row 1, row 3
+}
+
 template <int CTRL, typename T, int KI, int KO>
 __device__ __forceinline__ void tsum_step(const T (&in)[KI], T (&out)[KO], bool hi) {
 #pragma unroll

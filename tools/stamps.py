@@ -7,7 +7,7 @@ Runs the C2 workload through libbqp_stamps.so and prints the mean cycles per pha
 cycles per iteration), tagged with the sha1 of csrc/bqp_ocp.hip so that bench can tell whether
 the stamps were taken on the kernel source it runs.  --split: for a build with -DBQP_STAMPS_SPLIT as
 well, which stamps the first pass of solve() in three parts (right-hand side, pre-pass bodies, the
-wave_sync behind them)."""
+wave_sync behind them) and closes the factor phase behind factor(), prep_iter() joining the wait at B2."""
 import ctypes as C
 import hashlib
 import json
@@ -52,6 +52,8 @@ stage = ['wait B0 + residual combine', 'combine', 'wait B1', 'decide + factor', 
          'solves: theta + forward sweep', 'solves: post-forward']
 if split:
     stage[2] = 'solves: rhs'
+    stage[3] = 'decide + factor (alone)'
+    stage[4] = 'prep_iter + wait B2'
     stage[10] = 'solves: wave_sync behind the pre-pass'
     stage.append('solves: pre-pass bodies')
 row = ['wait B0', 'row residuals', 'rhs pred', 'wait B1,B2', 'wait B3',
